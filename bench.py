@@ -18,8 +18,14 @@ Users are range-split across ranks by cumulative k^3 (multi.cost_split) out of t
 global set: total work is fixed as N grows ("scaling": "strong").
 
 Prints ONE JSON line (rank 0).  `value` = user-subgraph eigendecomps/sec of the whole job
-through the step; predicted ratings/sec and per-stage rates are extra fields.  See DESIGN.md
-sec. 6 for the roofline accounting.
+through the step; predicted ratings/sec and per-stage rates are extra fields.
+
+A plain run does only what that line's headline needs: setup, warm-up, the timed steps, the
+outputs of the last step if --dump-outputs DIR is given, the line.  --full adds everything
+else to the same line: the roofline accounting (flop counts, one more eigen pass for the sweep
+counts, rocprofv3 --pmc traffic passes), the CPU baselines and the secondary legs (out_eigen_
+I/O, config 2, knn2, data prep, config 5).  The timed steps are the same either way.  See
+DESIGN.md sec. 6 for the roofline accounting.
 """
 from __future__ import annotations
 
@@ -53,13 +59,20 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: roofline accounting (flop counts, the sweep-count "
+                        "pass, PMC traffic), CPU baselines and the secondary legs (I/O, C2, knn2, prep, C5)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (rank 0's share) as DIR/<name>.npy: m of every "
+                        "user, the sigs / evals / mse / kk rows and the packed eigen records of a fixed seeded "
+                        "sample (see dump_outputs)")
     p.add_argument("--config", choices=sorted(CONFIGS), default="c4")
     p.add_argument("--users", type=int, default=0, help="global test users (default: the config's)")
     p.add_argument("--fused", choices=["on", "off"], default="off",
                    help="on: cf_step_run (per-bucket eigen/predict overlap); off: cf_eigen_run then cf_predict_run_f32")
     p.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample")
     p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--profile-steps-only", action="store_true", help="no legs, no PMC, no CPU baseline")
+    p.add_argument("--profile-steps-only", action="store_true", help="with --full: no legs, no PMC, no CPU baseline (the accounting only)")
     p.add_argument("--pmc", choices=["auto", "off"], default="auto",
                    help="N=1: HBM traffic from two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE)")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # one pass, no output
@@ -311,7 +324,9 @@ def main():
         # global set's (Workload.sig_table), which only the two-call step provides
         raise SystemExit("--fused on is single-rank only")
     cfg = CONFIGS[args.config]
-    solo = rank == 0 and world == 1 and not args.profile_steps_only and not args.pmc_child
+    # a plain run sets up, warms up, times the steps and prints the headline; the accounting
+    # passes, baselines and legs below are --full's
+    solo = args.full and rank == 0 and world == 1 and not args.profile_steps_only and not args.pmc_child
     want_cpu = solo and not args.no_cpu_baseline
 
     # ---- workload (untimed setup) -------------------------------------------------
@@ -423,11 +438,26 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # the last timed step's outputs, before any later pass touches the buffers
+    if args.dump_outputs and rank == 0:
+        phase("dump outputs")
+        dump_outputs(args.dump_outputs, wl, cfg["seed"])
+
     # per-stage durations: HIP events on the launch streams, recorded inside the timed steps
     gat_ms = [e[2].elapsed_time(e[3]) for e in evs]
     gat_s = float(np.median(gat_ms)) / 1e3
     overlap = None
-    if args.fused == "on":
+    if args.fused == "on" and not args.full:
+        # eigen = step start -> last eigen bucket (cf_step_timing; the predictor runs beside it);
+        # the predictor alone is one more pass, which --full takes
+        fused_ms = [e[0].elapsed_time(e[1]) for e in evs]
+        eig_s = float(np.median(fused_eig)) / 1e3
+        pred_s = None
+        overlap = {"fused_step_ms": float(np.median(fused_ms)), "eigen_span_ms": eig_s * 1e3,
+                   "note": "cf_step_run overlaps each k-bucket's predictor with the later eigen buckets; "
+                           "eigen_span = step start to the last eigen bucket inside the timed steps; --full "
+                           "adds the isolated stage times"}
+    elif args.fused == "on":
         # eigen = step start -> last eigen bucket (cf_step_timing; the predictor runs beside it);
         # the predictor's own duration is measured in isolation below (cf_predict_run_f32 alone)
         fused_ms = [e[0].elapsed_time(e[1]) for e in evs]
@@ -453,22 +483,8 @@ def main():
         pred_ms = [e[1].elapsed_time(e[2]) for e in evs]
         eig_s = float(np.median(eig_ms)) / 1e3
         pred_s = float(np.median(pred_ms)) / 1e3
-    # Jacobi sweep counts of one more (untimed) eigen pass, for the executed-flop estimate
-    # (one stream: every k-bucket alone on the GPU, timed too -- the dominant kernel's
-    # stand-alone duration, which a rocprofv3 average over the run's launches mixes in)
-    ctx.debug_stats(True)
-    ctx.eigen_bucket_timing(True)
-    wl.eigen(sp)
-    torch.cuda.synchronize(dev)
-    bucket_alone_ms, bucket_sw_alone_ms = ctx.eigen_bucket_timing(False, read=True, sweeps=True)
-    jstats = ctx.debug_stats(False, read=True)
 
     # ---- accounting -------------------------------------------------------------------
-    m_h = wl.d_m.cpu().numpy()[:wl.n_users]
-    kk_h = wl.d_kk.cpu().numpy()[:wl.n_entries]
-    mse_h = wl.d_mse.cpu().numpy()[:wl.n_entries]
-    evals_h = wl.d_evals.cpu().numpy()
-    sigs_h = wl.d_sigs.cpu().numpy()
     step_s = elapsed / args.steps
     n_pred_local = wl.n_entries
     if world > 1:
@@ -479,25 +495,40 @@ def main():
     else:
         n_pred_total = n_pred_local
     value = wl.U / step_s
-    roof_eigen = eigen_roofline(wl.k, m_h, eig_s, jstats, bucket_ms, bucket_alone_ms, bucket_sw_ms, bucket_sw_alone_ms)
-    pred_acc = predictor_flops(wl.off, wl.k, m_h, kk_h, evals_h, sigs_h)
-    roof_pred = predict_roofline(pred_acc, pred_s)
-    dominant_is_pred = pred_s >= eig_s
-    # the contract's roofline is the DOMINANT KERNEL's (the stage-level figure did
-    # not follow for it): eigen_kernel<12, true>'s algorithmic flops per launch over its mean
-    # in-step HIP-event duration at the top level; the stage-level numbers move to "stage"
-    dom = roof_eigen.get("dominant")
-    if dom and dom.get("achieved") is not None:
-        stage = {kk: roof_eigen.pop(kk) for kk in ("kernel", "achieved", "frac", "algorithmic_flops_per_stage",
-                                                   "algorithmic_bytes_per_stage", "algorithmic_GBps",
-                                                   "executed_flops_per_stage", "executed_TFLOPs", "executed_frac")
-                 if kk in roof_eigen}
-        stage["note"] = "the eigen stage as a whole: every k-bucket launch and the record pack over the stage span"
-        roof_eigen["stage"] = stage
-        roof_eigen.update({"kernel": dom["kernel"], "achieved": dom["achieved"], "frac": dom["frac"],
-                           "algorithmic_flops_per_launch": dom["flops_per_launch"],
-                           "ms_per_launch": dom["ms_per_launch"],
-                           "per_unit": "9k^3 + 4k^2 flops per user (SURVEY 8d) x the launch's users"})
+    if args.full:
+        # Jacobi sweep counts of one more (untimed) eigen pass, for the executed-flop estimate
+        # (one stream: every k-bucket alone on the GPU, timed too -- the dominant kernel's
+        # stand-alone duration, which a rocprofv3 average over the run's launches mixes in)
+        ctx.debug_stats(True)
+        ctx.eigen_bucket_timing(True)
+        wl.eigen(sp)
+        torch.cuda.synchronize(dev)
+        bucket_alone_ms, bucket_sw_alone_ms = ctx.eigen_bucket_timing(False, read=True, sweeps=True)
+        jstats = ctx.debug_stats(False, read=True)
+        m_h = wl.d_m.cpu().numpy()[:wl.n_users]
+        kk_h = wl.d_kk.cpu().numpy()[:wl.n_entries]
+        mse_h = wl.d_mse.cpu().numpy()[:wl.n_entries]
+        evals_h = wl.d_evals.cpu().numpy()
+        sigs_h = wl.d_sigs.cpu().numpy()
+        roof_eigen = eigen_roofline(wl.k, m_h, eig_s, jstats, bucket_ms, bucket_alone_ms, bucket_sw_ms, bucket_sw_alone_ms)
+        pred_acc = predictor_flops(wl.off, wl.k, m_h, kk_h, evals_h, sigs_h)
+        roof_pred = predict_roofline(pred_acc, pred_s)
+        dominant_is_pred = pred_s >= eig_s
+        # the contract's roofline is the DOMINANT KERNEL's (the stage-level figure did
+        # not follow for it): eigen_kernel<12, true>'s algorithmic flops per launch over its mean
+        # in-step HIP-event duration at the top level; the stage-level numbers move to "stage"
+        dom = roof_eigen.get("dominant")
+        if dom and dom.get("achieved") is not None:
+            stage = {kk: roof_eigen.pop(kk) for kk in ("kernel", "achieved", "frac", "algorithmic_flops_per_stage",
+                                                       "algorithmic_bytes_per_stage", "algorithmic_GBps",
+                                                       "executed_flops_per_stage", "executed_TFLOPs", "executed_frac")
+                     if kk in roof_eigen}
+            stage["note"] = "the eigen stage as a whole: every k-bucket launch and the record pack over the stage span"
+            roof_eigen["stage"] = stage
+            roof_eigen.update({"kernel": dom["kernel"], "achieved": dom["achieved"], "frac": dom["frac"],
+                               "algorithmic_flops_per_launch": dom["flops_per_launch"],
+                               "ms_per_launch": dom["ms_per_launch"],
+                               "per_unit": "9k^3 + 4k^2 flops per user (SURVEY 8d) x the launch's users"})
     devices = None
     if world > 1:
         coll_dev = dev if backend == "nccl" else torch.device("cpu")
@@ -540,33 +571,36 @@ def main():
         "predicted_ratings_per_s": n_pred_total / step_s,
         "stages": {
             "eigen_ms": eig_s * 1e3,
-            "predict_ms": pred_s * 1e3,
+            "predict_ms": pred_s * 1e3 if pred_s is not None else None,
             "gather_ms": gat_s * 1e3 if world > 1 else 0.0,
             "eigen_users_per_s": wl.n_users / eig_s,
-            "predict_ratings_per_s": n_pred_local / pred_s,
+            "predict_ratings_per_s": n_pred_local / pred_s if pred_s is not None else None,
             "rank0_users": wl.n_users,
             "fused": overlap,
             "note": "per-stage times are rank 0's (HIP events, median over the timed steps); with --fused on "
                     "eigen_ms is the eigen span of the overlapped step and predict_ms the predictor alone "
                     "(see fused); with --fused off eigen_ms includes the record pack",
         },
-        "roofline": roof_pred if dominant_is_pred else roof_eigen,
-        "roofline_other": roof_eigen if dominant_is_pred else roof_pred,
         "setup_s": setup_s,
-        "m_mean": float(m_h.mean()),
-        "kk_mean": float(kk_h.mean()),
-        "nan_predictions": int(np.isnan(mse_h).sum()),
-        "nc_gt_62_frac": float(np.mean((np.repeat(wl.k, wl.k) - kk_h) > 62)),
-        "rank_deficient_predictions": {
-            "rows": pred_acc["rank_deficient_rows"], "frac": pred_acc["rank_deficient_frac"],
-            "c0_rows": pred_acc["c0_rows"],
-            "clamp_bounds": at_bound_stats(wl.off, wl.k, m_h, kk_h, evals_h, sigs_h, wl.ratings, mse_h),
-            "note": "rank 0's rows with 0 < c < lim (U_CS^T U_CS singular): the reference's explicit inverse "
-                    "returns rounding noise clamped to [1, 5] there, this kernel the minimum-norm least-squares "
-                    "prediction (tests pin every fast-path row to numpy's min-norm solution and count the "
-                    "block-wide ones); clamp_bounds: the share of them at pred 1 or 5 (cpu_baseline.clamp_bounds "
-                    "has the oracle's share on its sample)"},
     }
+    if args.full:
+        result.update({
+            "roofline": roof_pred if dominant_is_pred else roof_eigen,
+            "roofline_other": roof_eigen if dominant_is_pred else roof_pred,
+            "m_mean": float(m_h.mean()),
+            "kk_mean": float(kk_h.mean()),
+            "nan_predictions": int(np.isnan(mse_h).sum()),
+            "nc_gt_62_frac": float(np.mean((np.repeat(wl.k, wl.k) - kk_h) > 62)),
+            "rank_deficient_predictions": {
+                "rows": pred_acc["rank_deficient_rows"], "frac": pred_acc["rank_deficient_frac"],
+                "c0_rows": pred_acc["c0_rows"],
+                "clamp_bounds": at_bound_stats(wl.off, wl.k, m_h, kk_h, evals_h, sigs_h, wl.ratings, mse_h),
+                "note": "rank 0's rows with 0 < c < lim (U_CS^T U_CS singular): the reference's explicit inverse "
+                        "returns rounding noise clamped to [1, 5] there, this kernel the minimum-norm least-squares "
+                        "prediction (tests pin every fast-path row to numpy's min-norm solution and count the "
+                        "block-wide ones); clamp_bounds: the share of them at pred 1 or 5 (cpu_baseline.clamp_bounds "
+                        "has the oracle's share on its sample)"},
+        })
 
     # ---- HBM traffic (rank 0, N=1): two rocprofv3 --pmc passes over one child step ------
     if solo and args.pmc == "auto":
@@ -642,6 +676,50 @@ def main():
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 1_000_000      # rating rows of the sample (sigs, evals, mse, kk: 4 MB each)
+DUMP_USERS = 128           # users whose packed k x m eigenvector blocks are kept (<= 130 KB each)
+DUMP_M_USERS = 4_000_000   # m is kept for every user up to this many (4 B each)
+
+
+def dump_outputs(out_dir, wl, seed):
+    """What the timed path left in the rank's output buffers, as float32 / float64 .npy files in
+    `out_dir` (about 45 MB for config 4, under 64 MB for any size).  The workload is seeded and so is the
+    sample, so two builds run with the same arguments write arrays that compare entry for entry:
+      m.npy               m of the first min(users, DUMP_M_USERS) users (cf_eigen_run)
+      sample_rows.npy     the sorted rating rows of the sample (float64 indices, seeded choice)
+      sigs.npy evals.npy  cf_eigen_run's per-row outputs at those rows
+      mse.npy kk.npy      cf_predict_run_f32's outputs at those rows (mse is NaN where kk = 0)
+      sample_users.npy    the sorted users whose eigenvector blocks are kept (float64 indices)
+      packed_offsets.npy  start of each kept user's block in packed_records.npy, and the total
+      packed_records.npy  those users' k x m blocks as cf_pack_eigen_run packed them"""
+    torch = wl.torch
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    n_rows = min(wl.n_entries, DUMP_ROWS)
+    rows = np.sort(rng.choice(wl.n_entries, size=n_rows, replace=False)) if n_rows < wl.n_entries \
+        else np.arange(wl.n_entries, dtype=np.int64)
+    n_us = min(wl.n_users, DUMP_USERS)
+    users = np.sort(rng.choice(wl.n_users, size=n_us, replace=False)) if n_us < wl.n_users \
+        else np.arange(wl.n_users, dtype=np.int64)
+    torch.cuda.synchronize(wl.d_m.device)
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    save("m", wl.d_m[:min(wl.n_users, DUMP_M_USERS)].cpu().numpy())
+    save("sample_rows", rows, np.float64)
+    d_rows = torch.from_numpy(rows.astype(np.int64)).to(wl.d_m.device)
+    for name, buf in (("sigs", wl.d_sigs), ("evals", wl.d_evals), ("mse", wl.d_mse), ("kk", wl.d_kk)):
+        save(name, buf[d_rows].cpu().numpy())
+    poff = wl.d_poff.cpu().numpy().astype(np.int64)
+    blocks = [wl.d_packed[int(poff[u]):int(poff[u + 1])].cpu().numpy() for u in users]
+    offs = np.zeros(len(users) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([len(b) for b in blocks])
+    save("sample_users", users, np.float64)
+    save("packed_offsets", offs, np.float64)
+    save("packed_records", np.concatenate(blocks) if blocks else np.zeros(0, np.float32))
 
 
 def eigen_roofline(k, m_h, eig_s, jstats, bucket_ms=None, bucket_alone_ms=None, sw_ms=None, sw_alone_ms=None):

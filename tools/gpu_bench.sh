@@ -1,7 +1,10 @@
-# Default bench run (N=1), JSON line + stderr progress into gpurun_out/
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out
+# Whole bench line (N=1, --full), JSON line + stderr progress into $BENCH_OUT (default bench_out/)
+# usage: bash tools/gpu_bench.sh [name] [extra bench args]
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
+out=${BENCH_OUT:-bench_out}
+mkdir -p $out
 name=${1:-r3_bench}
 shift
-timeout -k 10 1100 python -u bench.py "$@" > gpurun_out/$name.json 2> gpurun_out/$name.err
+timeout -k 10 1100 python -u bench.py --full "$@" > $out/$name.json 2> $out/$name.err
 echo bench_rc=$?
-tail -c 6000 gpurun_out/$name.json
+tail -c 6000 $out/$name.json
