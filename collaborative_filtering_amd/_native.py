@@ -14,7 +14,9 @@ LIB_PATH = os.environ.get("CF_MI355X_LIB") or os.path.join(_HERE, "libcf_mi355x.
 HOST_LIB_PATH = os.path.join(_HERE, "libcf_host.so")
 
 CF_OK = 0
+CF_EINVAL = -1
 CF_ERANGE = -4
+CF_ALS_MAX_D = 64
 CF_SIGS_OWN = 0
 CF_SIGS_COMPAT = 1
 CF_MAX_K = 192
@@ -112,6 +114,15 @@ SIGNATURES = {
                                   c_void_p]),
     "cf_eigen_batch_multi": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_uint64, c_void_p]),
+    "cf_als_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_double, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_als_error": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
+                             c_void_p, c_double, c_double, c_void_p]),
+    "cf_als_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p,
+                               c_void_p]),
+    "cf_debug_als_segment": (c_int, []),
+    "cf_debug_als_low_max": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }
@@ -128,6 +139,12 @@ class EigenStreamStats(ctypes.Structure):
     """cf_eigen_stream_stats (cf_abi.h)."""
     _fields_ = [("chunks", c_uint32), ("chunk_slot_bytes", c_uint64), ("max_chunk_slot_bytes", c_uint64),
                 ("own_peak_bytes", c_uint64), ("device_peak_bytes", c_uint64)]
+
+
+class AlsStats(ctypes.Structure):
+    """cf_als_stats (cf_abi.h)."""
+    _fields_ = [("supersteps", c_uint32), ("updates", c_uint64), ("n_not_pd", c_uint64),
+                ("update_ms", c_float), ("scatter_ms", c_float)]
 
 
 EIGEN_SINK = ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))

@@ -52,6 +52,41 @@ class EigenResult:
         return self.sigs[b:e], ev, U
 
 
+@dataclass
+class AlsResult:
+    """Outcome of Context.als_fit: fitted factors, per-vertex update counts and residuals
+    (user side, item side) and the cf_als_stats of the run."""
+
+    U: np.ndarray
+    V: np.ndarray
+    nupdates_user: np.ndarray
+    nupdates_item: np.ndarray
+    residual_user: np.ndarray
+    residual_item: np.ndarray
+    supersteps: int
+    updates: int
+    n_not_pd: int
+    update_ms: float
+    scatter_ms: float
+
+    @property
+    def nupdates(self):
+        return self.nupdates_user, self.nupdates_item
+
+    @property
+    def residual(self):
+        return self.residual_user, self.residual_item
+
+
+def _csr(row, col, obs, n_rows):
+    """Stable CSR of an edge list by row (edges of one row keep their input order)."""
+    perm = np.argsort(row, kind="stable")
+    off = np.zeros(n_rows + 1, dtype=np.uint64)
+    if n_rows:
+        off[1:] = np.cumsum(np.bincount(row, minlength=n_rows))
+    return off, np.ascontiguousarray(col[perm]), np.ascontiguousarray(obs[perm])
+
+
 class Context:
     """One device context (cf_ctx) holding the HBM-resident item graph."""
 
@@ -426,6 +461,90 @@ class Context:
         self._chk(self.lib.cf_graph_filter_timing(self.h, ptr(ms), ptr(ne)), "cf_graph_filter_timing")
         return out, float(ms[0]), int(ne[0])
 
+    # -- ALS matrix factorization (als.cpp:290-371) ---------------------------------
+    def als_fit(self, user, item, obs, n_users, n_items, U0, V0, *, lam=0.01, regnormal=True, out_degree=None,
+                tol=1e-3, max_updates=None, max_supersteps=0, activate_user=None, nupdates=None,
+                residual=None) -> "AlsResult":
+        """cf_als_fit over the TRAIN edges (user[e], item[e], obs[e]) from the initial factors
+        U0 (n_users x D), V0 (n_items x D).  Regularisation per vertex: regnormal=True is the
+        reference's default, lambda * num_out_edges -- out_degree per user (every role; None =
+        the TRAIN degree) and 0 for every item (als.cpp:323-327); regnormal="degree" is lambda *
+        TRAIN degree on both sides; False is plain lambda.  Superstep 0 updates the users with
+        activate_user != 0 (None: those with out_degree > 0, als.cpp:363-367).  nupdates /
+        residual: optional (user, item) pairs to continue from."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n_users, n_items = int(n_users), int(n_items)
+        U = np.array(U0, dtype=np.float64, order="C")
+        V = np.array(V0, dtype=np.float64, order="C")
+        # D from whichever side has vertices (an empty side may come as any empty array)
+        dims = {a.size // n for a, n in ((U, n_users), (V, n_items)) if n}
+        if len(dims) > 1:
+            raise ValueError("U0 and V0 differ in D")
+        D = dims.pop() if dims else (U.shape[1] if U.ndim == 2 and U.shape[1] else 1)
+        if U.size != n_users * D or V.size != n_items * D:
+            raise ValueError("U0 / V0 do not hold n_users x D / n_items x D values")
+        U, V = U.reshape(n_users, D), V.reshape(n_items, D)
+        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
+            raise ValueError("edge index out of range")
+        uoff, uitem, uobs = _csr(user, item, obs, n_users)
+        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        du = np.diff(uoff.astype(np.int64)).astype(np.float64)
+        di = np.diff(ioff.astype(np.int64)).astype(np.float64)
+        od = du if out_degree is None else np.asarray(out_degree, dtype=np.float64)
+        if regnormal == "degree":
+            ru, ri = lam * du, lam * di
+        elif regnormal:
+            ru, ri = lam * od, np.zeros(n_items)
+        else:
+            ru, ri = np.full(n_users, float(lam)), np.full(n_items, float(lam))
+        ru = np.ascontiguousarray(ru, dtype=np.float64)
+        ri = np.ascontiguousarray(ri, dtype=np.float64)
+        act = (od > 0) if activate_user is None else np.asarray(activate_user) != 0
+        act = np.ascontiguousarray(act, dtype=np.uint8)
+        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
+            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        rs = [np.zeros(n_users, np.float32), np.zeros(n_items, np.float32)] if residual is None else \
+            [np.array(residual[0], dtype=np.float32), np.array(residual[1], dtype=np.float32)]
+        st = _native.AlsStats()
+        cap = (1 << 64) - 1 if max_updates is None else int(max_updates)
+        self._chk(self.lib.cf_als_fit(self.h, n_users, n_items, int(D), ptr(uoff), ptr(uitem), ptr(uobs), ptr(ioff),
+                                      ptr(iuser), ptr(iobs), ptr(ru), ptr(ri), float(tol), cap, int(max_supersteps),
+                                      ptr(U), ptr(V), ptr(nu[0]), ptr(nu[1]), ptr(rs[0]), ptr(rs[1]), ptr(act),
+                                      byref(st)), "cf_als_fit")
+        return AlsResult(U, V, nu[0], nu[1], rs[0], rs[1], int(st.supersteps), int(st.updates), int(st.n_not_pd),
+                         float(st.update_ms), float(st.scatter_ms))
+
+    def als_sum_sq_error(self, user, item, obs, U, V, minval=-1e100, maxval=1e100) -> float:
+        """cf_als_error: sum over the edges of (obs - clamp(u.v, minval, maxval))^2."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        out = c_double()
+        self._chk(self.lib.cf_als_error(self.h, len(user), ptr(user), ptr(item), ptr(obs), U.shape[0], V.shape[0],
+                                        U.shape[1], ptr(U), ptr(V), float(minval), float(maxval), byref(out)),
+                  "cf_als_error")
+        return out.value
+
+    def als_rmse(self, user, item, obs, U, V, minval=-1e100, maxval=1e100) -> float:
+        """RMSE of one role's edges (error_aggregator::finalize, als.cpp:474-483)."""
+        n = len(user)
+        return float(np.sqrt(self.als_sum_sq_error(user, item, obs, U, V, minval, maxval) / n)) if n else 0.0
+
+    def als_predict(self, user, item, U, V) -> np.ndarray:
+        """cf_als_predict: u.v (unclamped) per (user, item) pair (als.cpp:499-509)."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        pred = np.zeros(len(user), dtype=np.float64)
+        self._chk(self.lib.cf_als_predict(self.h, len(user), ptr(user), ptr(item), U.shape[0], V.shape[0], U.shape[1],
+                                          ptr(U), ptr(V), ptr(pred)), "cf_als_predict")
+        return pred
+
     # -- device-resident paths (torch CUDA tensors) -------------------------------
     def plan(self, item_off_host) -> "Plan":
         return Plan(self, item_off_host)
@@ -626,6 +745,6 @@ class Plan:
                   ptr(d_pred), c_void_p(stream or 0)), "cf_predict_run")
 
 
-__all__ = ["Context", "Plan", "EigenResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
+__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
            "predict_precomp_multi", "CF_SIGS_OWN", "CF_SIGS_COMPAT", "CF_FILTER_CHEBY",
            "CF_FILTER_BINOMIAL"]

@@ -136,6 +136,7 @@ int cf_release_workspaces(cf_ctx* ctx) {
     drop(ctx->d_tri, ctx->tri_bytes);
     drop(ctx->d_scratch, ctx->scratch_bytes);
     drop(ctx->d_knn, ctx->knn_bytes);
+    drop(ctx->d_als, ctx->als_bytes);
     return CF_OK;
 }
 
@@ -160,6 +161,7 @@ void cf_destroy(cf_ctx* ctx) {
     if (ctx->d_knn_acc) (void)hipFree(ctx->d_knn_acc);
     if (ctx->d_knn_part) (void)hipFree(ctx->d_knn_part);
     if (ctx->d_prep) (void)hipFree(ctx->d_prep);
+    if (ctx->d_als) (void)hipFree(ctx->d_als);
     for (hipEvent_t& e : ctx->prep_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& run : ctx->bucket_ev)

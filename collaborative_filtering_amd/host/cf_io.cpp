@@ -243,6 +243,30 @@ std::vector<Rating> load_movielens(const std::string& dir, bool remap_users) {
     return out;
 }
 
+std::vector<RoleRating> load_movielens_roles(const std::string& dir) {
+    std::vector<RoleRating> out;
+    for (const auto& path : files_with_suffix(dir, "")) {
+        const uint8_t role = ends_with(path, ".validate") ? kValidate : (ends_with(path, ".predict") ? kPredict : kTrain);
+        const std::string text = read_file(path);
+        for_each_line(text, [&](const char* b, const char* e) {
+            Tok t{b, e};
+            const auto comma = [&t] {   // -qi::char_(',') under the space skipper
+                t.skip();
+                if (t.p < t.e && *t.p == ',') ++t.p;
+            };
+            uint32_t u, m;
+            double r = 0;
+            if (!t.u32(u)) return;
+            comma();
+            if (!t.u32(m)) return;
+            comma();
+            t.f64(r);
+            out.push_back({u, m, (float)r, role});
+        });
+    }
+    return out;
+}
+
 VertexRatings load_vertex_ratings(const std::string& dir, const std::string& prefix, bool require_nonempty) {
     VertexRatings out;
     for (const auto& path : files_with_prefix(dir, prefix)) {

@@ -42,6 +42,19 @@ struct Rating {
 // (knn.cpp:88-92); source id remapped to uimax - id (knn.cpp:103).
 std::vector<Rating> load_movielens(const std::string& dir, bool remap_users);
 
+// The ALS loader's view of movielens/* (als.cpp:379-417): role by file suffix -- TRAIN, VALIDATE
+// (".validate") or PREDICT (".predict") -- and lines "user item [rating]" separated by blanks,
+// tabs or one optional comma each (:397-399); the rating is parsed as a float and is 0 when
+// absent.  Ids are as written (no remap); lines that do not parse are skipped.
+enum Role : uint8_t { kTrain = 0, kValidate = 1, kPredict = 2 };
+struct RoleRating {
+    uint32_t user;
+    uint32_t item;
+    float obs;
+    uint8_t role;
+};
+std::vector<RoleRating> load_movielens_roles(const std::string& dir);
+
 // Per-vertex lines "id a b a b ..." (out_rat_, out_test_rat_): id -> [(user, rating)].
 using VertexRatings = std::unordered_map<uint32_t, std::vector<std::pair<uint32_t, double>>>;
 VertexRatings load_vertex_ratings(const std::string& dir, const std::string& prefix,

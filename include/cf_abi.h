@@ -28,6 +28,8 @@
  *                                  movie local graph, eigensolve, per-user w_lim, predict)
  *   cf_knn_predict               : knn_program gather/apply + error_vertex_data,
  *                                  knn3.cpp:185-256
+ *   cf_als_fit / _error / _predict : als_vertex_program, error_aggregator and prediction_saver,
+ *                                  als.cpp:290-371,424-510
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -61,7 +63,7 @@ int cf_device_count(void);
 int cf_create(int device, cf_ctx** out);
 void cf_destroy(cf_ctx* ctx);
 /* Waits for the context's device, then frees its cached HBM workspaces (eigen and predictor
- * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes); each is
+ * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS); each is
  * allocated again, at the size its next call plans, when that call runs.  The spill paths
  * size their workspaces from the device's free HBM, so a workspace the predictor left behind
  * shrinks the next eigen call's and costs it waves: call this between stages of a long-lived
@@ -480,6 +482,57 @@ int cf_graph_filter(cf_ctx* ctx, int kind, uint32_t n_vertices, uint64_t n_lines
                     uint32_t n_coeff, double* out);
 /* Device time of the last cf_graph_filter's supersteps (HIP events) and its directed edges. */
 int cf_graph_filter_timing(cf_ctx* ctx, float* device_ms, uint64_t* n_edges);
+
+/* ---- ALS matrix factorization (als.cpp:290-371 on the synchronous engine) ----------------
+ * R ~ U V^T over a bipartite graph: users 0..n_users-1 (the side with out-edges), items
+ * 0..n_items-1, TRAIN edges only.  Superstep 0 updates the users with activate_user[u] != 0
+ * (NULL = every user; the reference signals the users with an out-edge of any role,
+ * als.cpp:363-367,662); an update of vertex v (apply, als.cpp:313-334) solves
+ * (sum x_j x_j^T + reg[v] I) f = sum obs_j x_j over its edges by an unpivoted LDL^T of the upper
+ * triangle, sets residual[v] = (float)(|f - old|_1 / D) and nupdates[v] += 1 (a vertex without
+ * edges: residual 0, nupdates += 1, factor untouched); then (scatter, als.cpp:343-357) every
+ * edge of an updated vertex signals its other end for the next superstep iff
+ * (double)((float)|obs - u.v| * residual[v]) > tol and nupdates[other] < max_updates
+ * (UINT64_MAX = no cap).  The sides alternate; the run ends when nobody is signalled or after
+ * max_supersteps supersteps (0 = no cap).  fp64 throughout, no floating-point atomics: a
+ * vertex's new factor is the same bits whichever other vertices are active.
+ *   user_off / user_item / user_obs : CSR over users; item_off / item_user / item_obs : its
+ *       transpose (the per-vertex counts are checked: CF_EINVAL)
+ *   reg_user / reg_item : the value added to the diagonal per vertex (the reference: lambda, or
+ *       with regnormal lambda * num_out_edges, which is 0 for every item, als.cpp:323-327)
+ *   U [n_users * D], V [n_items * D] : in the initial factors (the reference draws them,
+ *       als.cpp:103), out the fitted ones; nupdates_* and residual_* in / out likewise
+ * An exactly zero pivot is skipped (cf_ldlt.hpp), pivots <= 0 are counted in n_not_pd; systems
+ * that are not positive definite are outside the parity claim (Eigen's ldlt pivots).
+ * D > CF_ALS_MAX_D gives CF_ERANGE; n_users == 0 or no edges is a valid call. */
+#define CF_ALS_MAX_D 64
+typedef struct cf_als_stats {
+    uint32_t supersteps;   /* supersteps run */
+    uint64_t updates;      /* vertex updates executed ("Updates executed", als.cpp:676) */
+    uint64_t n_not_pd;     /* pivots <= 0 met by the solves */
+    float update_ms;       /* device time of the update kernels (HIP events) */
+    float scatter_ms;      /* device time of the scatter and compaction kernels */
+} cf_als_stats;
+int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+               const uint32_t* user_item, const float* user_obs, const uint64_t* item_off,
+               const uint32_t* item_user, const float* item_obs, const double* reg_user,
+               const double* reg_item, double tol, uint64_t max_updates, uint32_t max_supersteps, double* U,
+               double* V, uint32_t* nupdates_user, uint32_t* nupdates_item, float* residual_user,
+               float* residual_item, const uint8_t* activate_user, cf_als_stats* stats);
+/* extract_l2_error summed over the edges of one role (als.cpp:424-430,465-473):
+ * *sum_sq = sum (obs - clamp(u.v, minval, maxval))^2; the caller divides and takes the root
+ * (:475-479).  A fixed two-level reduction: the same inputs give the same bits. */
+int cf_als_error(cf_ctx* ctx, uint64_t n_edges, const uint32_t* user, const uint32_t* item, const float* obs,
+                 uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
+                 double minval, double maxval, double* sum_sq);
+/* prediction_saver::save_edge (als.cpp:499-509): pred[p] = U[user[p]] . V[item[p]], unclamped. */
+int cf_als_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const uint32_t* item, uint32_t n_users,
+                   uint32_t n_items, uint32_t D, const double* U, const double* V, double* pred);
+/* The degree cuts of the update kernels (constants of cf_als.hip; test helpers): vertices with
+ * more TRAIN edges than the segment length are summed in segments of that length, vertices with
+ * at most low_max edges take one wave. */
+int cf_debug_als_segment(void);
+int cf_debug_als_low_max(void);
 
 #ifdef __cplusplus
 }
