@@ -121,6 +121,14 @@ SIGNATURES = {
                              c_void_p, c_double, c_double, c_void_p]),
     "cf_als_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p,
                                c_void_p]),
+    "cf_sgd_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "cf_sgd_timing": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cf_sgd_error": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
+    "cf_sgd_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_double, c_int, c_double, c_double, c_void_p]),
     "cf_debug_als_segment": (c_int, []),
     "cf_debug_als_low_max": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
@@ -145,6 +153,19 @@ class AlsStats(ctypes.Structure):
     """cf_als_stats (cf_abi.h)."""
     _fields_ = [("supersteps", c_uint32), ("updates", c_uint64), ("n_not_pd", c_uint64),
                 ("update_ms", c_float), ("scatter_ms", c_float)]
+
+
+class SgdParams(ctypes.Structure):
+    """cf_sgd_params (cf_abi.h)."""
+    _fields_ = [("lambda_", c_double), ("gamma", c_double), ("step_dec", c_double), ("tol", c_double),
+                ("minval", c_double), ("maxval", c_double), ("global_mean", c_double), ("max_updates", c_uint64),
+                ("max_supersteps", c_uint32)]
+
+
+class SgdStats(ctypes.Structure):
+    """cf_sgd_stats (cf_abi.h)."""
+    _fields_ = [("supersteps", c_uint32), ("updates", c_uint64), ("messages", c_uint64), ("n_nan", c_uint64),
+                ("gamma_next", c_double), ("reduce_ms", c_float), ("apply_ms", c_float)]
 
 
 EIGEN_SINK = ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))

@@ -78,6 +78,36 @@ class AlsResult:
         return self.residual_user, self.residual_item
 
 
+@dataclass
+class SgdResult:
+    """Outcome of Context.sgd_fit: fitted factors and biases (None for plain SGD), per-vertex
+    update counts, the trace (one row {sum sq err TRAIN, sum sq err VALIDATE} per user
+    superstep) and the cf_sgd_stats of the run; user_reduce_ms / item_reduce_ms split
+    reduce_ms by side (cf_sgd_timing)."""
+
+    U: np.ndarray
+    V: np.ndarray
+    bias_user: np.ndarray | None
+    bias_item: np.ndarray | None
+    nupdates_user: np.ndarray
+    nupdates_item: np.ndarray
+    trace: np.ndarray
+    global_mean: float
+    supersteps: int
+    updates: int
+    messages: int
+    n_nan: int
+    gamma_next: float
+    reduce_ms: float
+    apply_ms: float
+    user_reduce_ms: float
+    item_reduce_ms: float
+
+    @property
+    def nupdates(self):
+        return self.nupdates_user, self.nupdates_item
+
+
 def _csr(row, col, obs, n_rows):
     """Stable CSR of an edge list by row (edges of one row keep their input order)."""
     perm = np.argsort(row, kind="stable")
@@ -545,6 +575,119 @@ class Context:
                                           ptr(U), ptr(V), ptr(pred)), "cf_als_predict")
         return pred
 
+    # -- SGD / bias-SGD matrix factorization (sgd.cpp, biassgd.cpp) ----------------------
+    def sgd_fit(self, user, item, obs, n_users, n_items, U0, V0, *, bias=False, lam=0.001, gamma=0.001, step_dec=0.9,
+                tol=1e-3, minval=-1e100, maxval=1e100, global_mean=None, bias_user=None, bias_item=None,
+                max_updates=None, max_supersteps=0, activate_user=None, nupdates=None, validate=None,
+                trace=True) -> "SgdResult":
+        """cf_sgd_fit over the TRAIN edges (user[e], item[e], obs[e]) from the initial factors U0
+        (n_users x D), V0 (n_items x D).  bias=True is bias-SGD: biases start at bias_user /
+        bias_item (None: zeros) and global_mean defaults to the fp64 mean of the TRAIN ratings
+        (biassgd.cpp:684-686).  Superstep 0 updates the users with activate_user != 0 (None:
+        every user).  One of max_updates / max_supersteps is mandatory (the reference never stops
+        without a cap).  validate: optional (user, item, obs) of the VALIDATE edges for the
+        trace's second column.  nupdates: optional (user, item) pair to continue from."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n_users, n_items = int(n_users), int(n_items)
+        U = np.array(U0, dtype=np.float64, order="C")
+        V = np.array(V0, dtype=np.float64, order="C")
+        dims = {a.size // n for a, n in ((U, n_users), (V, n_items)) if n}
+        if len(dims) > 1:
+            raise ValueError("U0 and V0 differ in D")
+        D = dims.pop() if dims else (U.shape[1] if U.ndim == 2 and U.shape[1] else 1)
+        if U.size != n_users * D or V.size != n_items * D:
+            raise ValueError("U0 / V0 do not hold n_users x D / n_items x D values")
+        U, V = U.reshape(n_users, D), V.reshape(n_items, D)
+        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
+            raise ValueError("edge index out of range")
+        uoff, uitem, uobs = _csr(user, item, obs, n_users)
+        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        bu = bi = None
+        mean = 0.0
+        if bias:
+            bu = np.zeros(n_users) if bias_user is None else np.array(bias_user, dtype=np.float64)
+            bi = np.zeros(n_items) if bias_item is None else np.array(bias_item, dtype=np.float64)
+            if global_mean is None:
+                mean = float(obs.astype(np.float64).sum() / len(obs)) if len(obs) else 0.0
+            else:
+                mean = float(global_mean)
+        act = None if activate_user is None else np.ascontiguousarray(np.asarray(activate_user) != 0, dtype=np.uint8)
+        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
+            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        cap = (1 << 64) - 1 if max_updates is None else int(max_updates)
+        max_supersteps = int(max_supersteps)
+        rows = 0
+        if trace:   # one row per user superstep, bounded by whichever cap is set
+            bounds = [(max_supersteps + 1) // 2] if max_supersteps else []
+            if max_updates is not None:
+                bounds.append(int(max_updates) + 1)
+            rows = min(bounds) if bounds else 0
+        tr = np.zeros((max(rows, 1), 2))
+        vu = vi = vo = None
+        if validate is not None and len(validate[0]):
+            vu = np.ascontiguousarray(validate[0], dtype=np.uint32)
+            vi = np.ascontiguousarray(validate[1], dtype=np.uint32)
+            vo = np.ascontiguousarray(validate[2], dtype=np.float32)
+        par = _native.SgdParams(float(lam), float(gamma), float(step_dec), float(tol), float(minval), float(maxval),
+                                mean, cap, max_supersteps)
+        st = _native.SgdStats()
+        self._chk(self.lib.cf_sgd_fit(self.h, n_users, n_items, int(D), ptr(uoff), ptr(uitem), ptr(uobs), ptr(ioff),
+                                      ptr(iuser), ptr(iobs), byref(par), ptr(U), ptr(V), ptr(bu), ptr(bi), ptr(nu[0]),
+                                      ptr(nu[1]), ptr(act), 0 if vu is None else len(vu), ptr(vu), ptr(vi), ptr(vo),
+                                      ptr(tr) if rows else None, rows, byref(st)), "cf_sgd_fit")
+        ums, ims = c_float(), c_float()
+        self._chk(self.lib.cf_sgd_timing(self.h, byref(ums), byref(ims)), "cf_sgd_timing")
+        done = min(rows, (int(st.supersteps) + 1) // 2)
+        return SgdResult(U, V, bu, bi, nu[0], nu[1], tr[:done].copy(), mean, int(st.supersteps), int(st.updates),
+                         int(st.messages), int(st.n_nan), float(st.gamma_next), float(st.reduce_ms), float(st.apply_ms),
+                         float(ums.value), float(ims.value))
+
+    def sgd_sum_sq_error(self, user, item, obs, U, V, bias_user=None, bias_item=None, global_mean=0.0,
+                         minval=-1e100, maxval=1e100) -> float:
+        """cf_sgd_error: sum over the edges of (obs - clamp(mean + bu + bi + u.v, minval, maxval))^2;
+        without biases the mean is ignored (plain SGD)."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
+        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
+        out = c_double()
+        self._chk(self.lib.cf_sgd_error(self.h, len(user), ptr(user), ptr(item), ptr(obs), U.shape[0], V.shape[0],
+                                        U.shape[1], ptr(U), ptr(V), ptr(bu), ptr(bi), float(global_mean), float(minval),
+                                        float(maxval), byref(out)), "cf_sgd_error")
+        return out.value
+
+    def sgd_rmse(self, user, item, obs, U, V, bias_user=None, bias_item=None, global_mean=0.0, minval=-1e100,
+                 maxval=1e100) -> float:
+        """RMSE of one role's edges (error_aggregator::finalize, sgd.cpp:372-387)."""
+        n = len(user)
+        if not n:
+            return 0.0
+        return float(np.sqrt(self.sgd_sum_sq_error(user, item, obs, U, V, bias_user, bias_item, global_mean, minval,
+                                                   maxval) / n))
+
+    def sgd_predict(self, user, item, U, V, bias_user=None, bias_item=None, global_mean=0.0, clamp=None,
+                    minval=-1e100, maxval=1e100) -> np.ndarray:
+        """cf_sgd_predict per (user, item) pair.  clamp None: as the reference's savers, clamped
+        with biases (biassgd.cpp:423-428), unclamped without (sgd.cpp:418-419)."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
+        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
+        if clamp is None:
+            clamp = bu is not None
+        pred = np.zeros(len(user), dtype=np.float64)
+        self._chk(self.lib.cf_sgd_predict(self.h, len(user), ptr(user), ptr(item), U.shape[0], V.shape[0], U.shape[1],
+                                          ptr(U), ptr(V), ptr(bu), ptr(bi), float(global_mean), int(bool(clamp)),
+                                          float(minval), float(maxval), ptr(pred)), "cf_sgd_predict")
+        return pred
+
     # -- device-resident paths (torch CUDA tensors) -------------------------------
     def plan(self, item_off_host) -> "Plan":
         return Plan(self, item_off_host)
@@ -745,6 +888,6 @@ class Plan:
                   ptr(d_pred), c_void_p(stream or 0)), "cf_predict_run")
 
 
-__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
+__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "SgdResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
            "predict_precomp_multi", "CF_SIGS_OWN", "CF_SIGS_COMPAT", "CF_FILTER_CHEBY",
            "CF_FILTER_BINOMIAL"]

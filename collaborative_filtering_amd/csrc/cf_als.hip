@@ -18,7 +18,7 @@
 // nnz (8 D + 8) bytes (one D-long fp64 row, the neighbour id and the rating per edge) and does
 // nnz D (D + 1) flops: bound by the row gathers, not by the fp64 units.
 //
-// Work is shaped by the vertex's TRAIN degree, with cuts that are constants of this file:
+// Work is shaped by the vertex's TRAIN degree, with cuts that are constants of cf_mf_common.h:
 //   low   deg <= kLowMax           one wave per vertex, kWaves vertices per workgroup
 //   mid   kLowMax < deg <= kSeg    one workgroup per vertex: its waves take contiguous quarters
 //                                  of the list, the partial (A, b) are summed in wave order in LDS
@@ -47,18 +47,11 @@
 
 #include "cf_internal.h"
 #include "cf_ldlt.hpp"
+#include "cf_mf_common.h"
 
 namespace {
 
-constexpr int kAT = 256;               // threads per workgroup
-constexpr int kWaves = kAT / 64;
 constexpr int kBatch = 16;             // neighbour rows staged per wave at a time
-constexpr int kLowMax = 64;            // low / mid cut (TRAIN degree)
-constexpr int kSeg = 2048;             // mid / high cut and the segment length
-constexpr int kG = 8;                  // lanes per edge of the dot-product kernels
-constexpr int kVPT = 4;                // vertices per thread of the compaction kernels
-constexpr int kCompBlock = kAT * kVPT;
-constexpr int kErrPerBlock = (kAT / kG) * 8;   // edges per block of the error kernel
 
 __host__ __device__ constexpr int sys_len(int D) { return (D + 1) * (D + 2) / 2; }   // packed rows 0..D
 
@@ -75,18 +68,6 @@ struct AlsSide {
     float* resid;
     uint8_t* flag;         // signalled for the next superstep of this side
     uint8_t* active;       // active in the current superstep of this side
-};
-
-// The compacted active lists of the side being updated (ascending vertex order).
-struct AlsLists {
-    uint32_t* low;
-    uint32_t* mid;
-    uint32_t* high;
-    uint32_t* high_base;   // first workspace slot (= index into seg_*) of each high vertex
-    uint32_t* seg_vertex;  // one entry per (high vertex, segment)
-    uint32_t* seg_index;
-    uint32_t* block_cnt;   // 4 counters per compaction block, then their exclusive scan
-    uint32_t* record;      // {low, mid, high, segments} of the last compaction
 };
 
 template <int DP>
@@ -321,110 +302,6 @@ __global__ __launch_bounds__(kAT) void als_finish_kernel(AlsSide s, int D, const
     wave_apply(S, D, s, v, not_pd, lane);
 }
 
-// ---- compaction of one side's flags into the class lists (deterministic scan) ------------
-
-__device__ __forceinline__ int als_class(uint64_t deg) { return deg <= (uint64_t)kLowMax ? 0 : (deg <= (uint64_t)kSeg ? 1 : 2); }
-
-// Exclusive scan of one value per thread over the block (kAT threads); *total = the block sum.
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave /* kWaves + 1 */, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();   // s_wave may still be read from the previous call
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t c = s_wave[w];
-        if (w < wave) before += c;
-        all += c;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-// FILL = false: per-block counters {low, mid, high, segments}.  FILL = true: with their exclusive
-// scan in block_cnt, writes the lists, sets active[] and clears flag[].
-template <bool FILL>
-__global__ __launch_bounds__(kAT) void als_compact_kernel(AlsSide s, AlsLists L) {
-    __shared__ uint32_t s_wave[kWaves + 1];
-    const uint32_t v0 = (blockIdx.x * (uint32_t)kAT + threadIdx.x) * kVPT;
-    uint32_t cnt[4] = {0, 0, 0, 0};
-    int cls[kVPT];
-    uint32_t nseg[kVPT];
-#pragma unroll
-    for (int i = 0; i < kVPT; ++i) {
-        cls[i] = -1;
-        nseg[i] = 0;
-        const uint64_t v = (uint64_t)v0 + i;
-        if (v < s.n && s.flag[v]) {
-            const uint64_t deg = s.off[v + 1] - s.off[v];
-            cls[i] = als_class(deg);
-            cnt[cls[i]]++;
-            if (cls[i] == 2) {
-                nseg[i] = (uint32_t)((deg + kSeg - 1) / kSeg);
-                cnt[3] += nseg[i];
-            }
-        }
-    }
-    uint32_t pre[4], tot[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) pre[c] = block_excl_scan(cnt[c], s_wave, &tot[c]);
-    if (!FILL) {
-        if (threadIdx.x == 0)
-            for (int c = 0; c < 4; ++c) L.block_cnt[(size_t)blockIdx.x * 4 + c] = tot[c];
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) pre[c] += L.block_cnt[(size_t)blockIdx.x * 4 + c];
-#pragma unroll
-    for (int i = 0; i < kVPT; ++i) {
-        const uint64_t v = (uint64_t)v0 + i;
-        if (v >= s.n) continue;
-        s.active[v] = cls[i] >= 0;
-        s.flag[v] = 0;
-        if (cls[i] == 0) L.low[pre[0]++] = (uint32_t)v;
-        else if (cls[i] == 1) L.mid[pre[1]++] = (uint32_t)v;
-        else if (cls[i] == 2) {
-            L.high[pre[2]] = (uint32_t)v;
-            L.high_base[pre[2]++] = pre[3];
-            for (uint32_t q = 0; q < nseg[i]; ++q) {
-                L.seg_vertex[pre[3]] = (uint32_t)v;
-                L.seg_index[pre[3]++] = q;
-            }
-        }
-    }
-}
-
-// Exclusive scan of the per-block counters in block order (one workgroup; counter c by thread c);
-// the totals go to the record.
-__global__ void als_scan_kernel(AlsLists L, uint32_t n_blocks) {
-    const int c = threadIdx.x;
-    if (c >= 4) return;
-    uint32_t run = 0;
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-        const uint32_t t = L.block_cnt[(size_t)b * 4 + c];
-        L.block_cnt[(size_t)b * 4 + c] = run;
-        run += t;
-    }
-    L.record[c] = run;
-}
-
-// ---- dot-product kernels: kG lanes per edge ---------------------------------------------
-
-__device__ __forceinline__ double group_dot(const double* __restrict__ a, const double* __restrict__ b, int D, int sl) {
-    double s = 0.0;
-    for (int d = sl; d < D; d += kG) s = fma(a[d], b[d], s);
-#pragma unroll
-    for (int o = kG / 2; o >= 1; o >>= 1) s += __shfl_xor(s, o, kG);
-    return s;
-}
-
 // scatter (als.cpp:343-357) over every edge of the side just updated; edges of inactive
 // vertices leave at once.  The flag stores are plain and all write the same value.
 __global__ __launch_bounds__(kAT) void als_scatter_kernel(AlsSide s, uint64_t nnz, const double* __restrict__ Fo,
@@ -444,87 +321,7 @@ __global__ __launch_bounds__(kAT) void als_scatter_kernel(AlsSide s, uint64_t nn
     if (priority > tol && (uint64_t)nupd_o[o] < max_updates) flag_o[o] = 1;
 }
 
-__global__ __launch_bounds__(kAT) void als_predict_kernel(uint64_t n, const uint32_t* __restrict__ user,
-                                                         const uint32_t* __restrict__ item, const double* __restrict__ U,
-                                                         const double* __restrict__ V, int D, double* pred) {
-    const uint64_t e = ((uint64_t)blockIdx.x * kAT + threadIdx.x) / kG;
-    const int sl = threadIdx.x & (kG - 1);
-    if (e >= n) return;
-    const double p = group_dot(U + (size_t)user[e] * D, V + (size_t)item[e] * D, D, sl);
-    if (sl == 0) pred[e] = p;
-}
-
-// Fixed tree over the block's kAT values in LDS; the result is in v[0].
-__device__ inline void block_tree_sum(double* v) {
-    for (int o = kAT / 2; o >= 1; o >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < o) v[threadIdx.x] += v[threadIdx.x + o];
-    }
-    __syncthreads();
-}
-
-// error aggregate (als.cpp:424-430), level 1: block b sums the clamped squared errors of edges
-// [b kErrPerBlock, (b + 1) kErrPerBlock): group g takes edges g, g + 32, .. in order, then a tree.
-__global__ __launch_bounds__(kAT) void als_error_kernel(uint64_t n, const uint32_t* __restrict__ user,
-                                                       const uint32_t* __restrict__ item, const float* __restrict__ obs,
-                                                       const double* __restrict__ U, const double* __restrict__ V, int D,
-                                                       double minval, double maxval, double* partial) {
-    __shared__ double s_v[kAT];
-    const int grp = threadIdx.x / kG, sl = threadIdx.x & (kG - 1);
-    const uint64_t e0 = (uint64_t)blockIdx.x * kErrPerBlock;
-    double acc = 0.0;
-    for (int r = 0; r < kErrPerBlock / (kAT / kG); ++r) {
-        const uint64_t e = e0 + (uint64_t)r * (kAT / kG) + grp;
-        if (e >= n) break;   // per group
-        double p = group_dot(U + (size_t)user[e] * D, V + (size_t)item[e] * D, D, sl);
-        p = fmin(maxval, p);
-        p = fmax(minval, p);
-        const double d = (double)obs[e] - p;
-        acc = fma(d, d, acc);
-    }
-    s_v[threadIdx.x] = sl == 0 ? acc : 0.0;
-    block_tree_sum(s_v);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_v[0];
-}
-
-// level 2: one workgroup; thread t sums partials t, t + kAT, .. in order, then the same tree.
-__global__ __launch_bounds__(kAT) void als_error_final_kernel(const double* __restrict__ partial, uint64_t n_partial,
-                                                             double* out) {
-    __shared__ double s_v[kAT];
-    double acc = 0.0;
-    for (uint64_t i = threadIdx.x; i < n_partial; i += kAT) acc += partial[i];
-    s_v[threadIdx.x] = acc;
-    block_tree_sum(s_v);
-    if (threadIdx.x == 0) *out = s_v[0];
-}
-
 // ---- host ---------------------------------------------------------------------------------
-
-// Carves one device allocation (the context's ALS workspace) into aligned arrays.
-struct Carver {
-    size_t pos = 0;
-    char* base = nullptr;
-    template <class T>
-    T* take(size_t count) {
-        const size_t at = pos;
-        pos = (pos + sizeof(T) * std::max<size_t>(count, 1) + 255) & ~(size_t)255;
-        return base ? reinterpret_cast<T*>(base + at) : nullptr;
-    }
-};
-
-// The context's ALS workspace with at least `bytes` bytes; grown before any launch of the call.
-int als_reserve(cf_ctx* ctx, size_t bytes) {
-    if (ctx->als_bytes >= bytes && ctx->d_als) return CF_OK;
-    if (ctx->d_als) {
-        CF_HIP_CHECK(ctx, hipDeviceSynchronize());
-        (void)hipFree(ctx->d_als);
-        ctx->d_als = nullptr;
-        ctx->als_bytes = 0;
-    }
-    CF_TRY(cf_malloc_evict(ctx, &ctx->d_als, bytes, "ALS workspace"));
-    ctx->als_bytes = bytes;
-    return CF_OK;
-}
 
 struct FitLayout {
     AlsSide side[2];
@@ -533,15 +330,6 @@ struct FitLayout {
     unsigned long long* not_pd;
     uint32_t seg_cap;
 };
-
-uint64_t total_segments(uint32_t n, const uint64_t* off) {
-    uint64_t segs = 0;
-    for (uint32_t v = 0; v < n; ++v) {
-        const uint64_t deg = off[v + 1] - off[v];
-        if (deg > (uint64_t)kSeg) segs += (deg + kSeg - 1) / kSeg;
-    }
-    return segs;
-}
 
 void carve_fit(Carver& c, FitLayout& f, uint32_t n_users, uint32_t n_items, uint64_t nnz, int D, uint64_t seg_cap) {
     const uint32_t n[2] = {n_users, n_items};
@@ -560,14 +348,7 @@ void carve_fit(Carver& c, FitLayout& f, uint32_t n_users, uint32_t n_items, uint
         s.active = c.take<uint8_t>(n[k]);
     }
     const size_t nmax = std::max(n_users, n_items);
-    f.lists.low = c.take<uint32_t>(nmax);
-    f.lists.mid = c.take<uint32_t>(nmax);
-    f.lists.high = c.take<uint32_t>(nmax);
-    f.lists.high_base = c.take<uint32_t>(nmax);
-    f.lists.seg_vertex = c.take<uint32_t>(seg_cap);
-    f.lists.seg_index = c.take<uint32_t>(seg_cap);
-    f.lists.block_cnt = c.take<uint32_t>(((nmax + kCompBlock - 1) / kCompBlock) * 4);
-    f.lists.record = c.take<uint32_t>(4);
+    carve_lists(c, f.lists, nmax, seg_cap);
     f.ws = c.take<double>((size_t)seg_cap * sys_len(D));
     f.not_pd = c.take<unsigned long long>(1);
     f.seg_cap = (uint32_t)seg_cap;
@@ -591,56 +372,6 @@ void launch_update(const FitLayout& f, int k, int D, const uint32_t rec[4], hipS
     }
 }
 
-void launch_compact(const FitLayout& f, int k, hipStream_t st) {
-    const AlsSide& s = f.side[k];
-    const uint32_t blocks = (uint32_t)(((uint64_t)s.n + kCompBlock - 1) / kCompBlock);
-    if (blocks) {
-        hipLaunchKernelGGL(als_compact_kernel<false>, dim3(blocks), dim3(kAT), 0, st, s, f.lists);
-        hipLaunchKernelGGL(als_scan_kernel, dim3(1), dim3(64), 0, st, f.lists, blocks);
-        hipLaunchKernelGGL(als_compact_kernel<true>, dim3(blocks), dim3(kAT), 0, st, s, f.lists);
-    } else {
-        hipLaunchKernelGGL(als_scan_kernel, dim3(1), dim3(64), 0, st, f.lists, 0u);
-    }
-}
-
-struct AlsEvents {   // destroyed on every return path
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~AlsEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-// Per-vertex degree counts of one CSR against the other's neighbour lists (the transpose check).
-bool transpose_counts_agree(uint32_t n_a, const uint64_t* off_a, const uint32_t* nbr_a, uint32_t n_b,
-                            const uint64_t* off_b) {
-    std::vector<uint64_t> cnt(n_b, 0);
-    for (uint64_t e = 0; e < off_a[n_a]; ++e) cnt[nbr_a[e]]++;
-    for (uint32_t v = 0; v < n_b; ++v)
-        if (cnt[v] != off_b[v + 1] - off_b[v]) return false;
-    return true;
-}
-
-int check_csr(cf_ctx* ctx, const char* what, uint32_t n, const uint64_t* off, const uint32_t* nbr, uint32_t n_other) {
-    if (off[0] != 0) return cf_set_error(ctx, CF_EINVAL, std::string("cf_als_fit: ") + what + " offsets do not start at 0");
-    for (uint32_t v = 0; v < n; ++v)
-        if (off[v + 1] < off[v]) return cf_set_error(ctx, CF_EINVAL, std::string("cf_als_fit: ") + what + " offsets decrease");
-    for (uint64_t e = 0; e < off[n]; ++e)
-        if (nbr[e] >= n_other) return cf_set_error(ctx, CF_EINVAL, std::string("cf_als_fit: ") + what + " index out of range");
-    return CF_OK;
-}
-
-int check_pairs(cf_ctx* ctx, const char* fn, uint64_t n, const uint32_t* user, const uint32_t* item, const double* U,
-                const double* V, uint32_t D, uint32_t n_users, uint32_t n_items) {
-    if (D == 0) return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": D = 0");
-    if (D > CF_ALS_MAX_D) return cf_set_error(ctx, CF_ERANGE, std::string(fn) + ": D above CF_ALS_MAX_D");
-    if (n && (!user || !item || !U || !V)) return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": null argument");
-    for (uint64_t e = 0; e < n; ++e)
-        if (user[e] >= n_users || item[e] >= n_items)
-            return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": index out of range");
-    return CF_OK;
-}
-
 }  // namespace
 
 extern "C" int cf_debug_als_segment(void) { return kSeg; }
@@ -659,16 +390,9 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     if ((n_users && (!user_off || !reg_user || !U || !nupdates_user || !residual_user)) ||
         (n_items && (!item_off || !reg_item || !V || !nupdates_item || !residual_item)))
         return cf_set_error(ctx, CF_EINVAL, "cf_als_fit: null argument");
-    const uint64_t nnz = n_users ? user_off[n_users] : 0;
-    const uint64_t nnz_i = n_items ? item_off[n_items] : 0;
-    if (nnz != nnz_i) return cf_set_error(ctx, CF_EINVAL, "cf_als_fit: the two CSRs hold different edge counts");
-    if (nnz && (!user_item || !user_obs || !item_user || !item_obs))
-        return cf_set_error(ctx, CF_EINVAL, "cf_als_fit: null edge array");
-    if (n_users) CF_TRY(check_csr(ctx, "user", n_users, user_off, user_item, n_items));
-    if (n_items) CF_TRY(check_csr(ctx, "item", n_items, item_off, item_user, n_users));
-    if (nnz && (!transpose_counts_agree(n_users, user_off, user_item, n_items, item_off) ||
-                !transpose_counts_agree(n_items, item_off, item_user, n_users, user_off)))
-        return cf_set_error(ctx, CF_EINVAL, "cf_als_fit: the per-vertex edge counts of the user CSR and the item CSR disagree");
+    uint64_t nnz = 0;
+    CF_TRY(check_two_csr(ctx, "cf_als_fit", n_users, n_items, D, user_off, user_item, user_obs, item_off, item_user,
+                         item_obs, &nnz));
     if (n_users == 0) return CF_OK;   // nothing can be active
     CF_TRY(set_device(ctx));
 
@@ -684,7 +408,7 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         c.base = static_cast<char*>(ctx->d_als);
         carve_fit(c, f, n_users, n_items, nnz, (int)D, seg_cap);
     }
-    AlsEvents evs;
+    MfEvents<3> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
     hipStream_t st = nullptr;
 
@@ -725,7 +449,7 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     uint64_t updates = 0;
     double update_ms = 0.0, scatter_ms = 0.0;
     int k = 0;   // the side being updated: users first (als.cpp:363-367,662)
-    launch_compact(f, k, st);
+    launch_compact(f.side[k], f.lists, st);
     for (;;) {
         // the one small record of the superstep: the active counts per class and the segments
         uint32_t rec[4];
@@ -755,7 +479,7 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
                                (const double*)f.side[1 - k].F, (const uint32_t*)f.side[1 - k].nupd, f.side[1 - k].flag,
                                (int)D, tol, max_updates);
         k = 1 - k;
-        launch_compact(f, k, st);
+        launch_compact(f.side[k], f.lists, st);
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
         ++supersteps;
         updates += n_active;
@@ -780,41 +504,6 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     return CF_OK;
 }
 
-namespace {
-
-// Uploads the pair list and both factor matrices into the context's ALS workspace.
-struct PairLayout {
-    uint32_t* user;
-    uint32_t* item;
-    float* obs;
-    double* U;
-    double* V;
-    double* out;       // predictions, or the block partials followed by the sum
-};
-
-int upload_pairs(cf_ctx* ctx, PairLayout& p, uint64_t n, const uint32_t* user, const uint32_t* item, const float* obs,
-                 uint32_t nu, uint32_t ni, uint32_t D, const double* U, const double* V, size_t n_out) {
-    for (int pass = 0; pass < 2; ++pass) {
-        Carver c;
-        if (pass) c.base = static_cast<char*>(ctx->d_als);
-        p.user = c.take<uint32_t>(n);
-        p.item = c.take<uint32_t>(n);
-        p.obs = c.take<float>(n);
-        p.U = c.take<double>((size_t)nu * D);
-        p.V = c.take<double>((size_t)ni * D);
-        p.out = c.take<double>(n_out);
-        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
-    }
-    CF_HIP_CHECK(ctx, hipMemcpy(p.user, user, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(p.item, item, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    if (obs) CF_HIP_CHECK(ctx, hipMemcpy(p.obs, obs, sizeof(float) * n, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(p.U, U, sizeof(double) * (size_t)nu * D, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(p.V, V, sizeof(double) * (size_t)ni * D, hipMemcpyHostToDevice));
-    return CF_OK;
-}
-
-}  // namespace
-
 extern "C" int cf_als_error(cf_ctx* ctx, uint64_t n_edges, const uint32_t* user, const uint32_t* item, const float* obs,
                             uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
                             double minval, double maxval, double* sum_sq) {
@@ -825,15 +514,12 @@ extern "C" int cf_als_error(cf_ctx* ctx, uint64_t n_edges, const uint32_t* user,
     if (n_edges && !obs) return cf_set_error(ctx, CF_EINVAL, "cf_als_error: null ratings");
     if (n_edges == 0) return CF_OK;
     CF_TRY(set_device(ctx));
-    const uint64_t blocks = (n_edges + kErrPerBlock - 1) / kErrPerBlock;
+    const uint64_t blocks = error_blocks(n_edges);
     if (blocks > 0x7fffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_als_error: too many edges");
     PairLayout p{};
     CF_TRY(upload_pairs(ctx, p, n_edges, user, item, obs, n_users, n_items, D, U, V, (size_t)blocks + 1));
-    hipLaunchKernelGGL(als_error_kernel, dim3((unsigned)blocks), dim3(kAT), 0, nullptr, n_edges, (const uint32_t*)p.user,
-                       (const uint32_t*)p.item, (const float*)p.obs, (const double*)p.U, (const double*)p.V, (int)D,
-                       minval, maxval, p.out);
-    hipLaunchKernelGGL(als_error_final_kernel, dim3(1), dim3(kAT), 0, nullptr, (const double*)p.out, blocks,
-                       p.out + blocks);
+    launch_error(nullptr, n_edges, p.user, p.item, p.obs, p.U, p.V, (int)D, nullptr, nullptr, 0.0, minval, maxval, p.out,
+                 p.out + blocks);
     CF_HIP_CHECK(ctx, hipGetLastError());
     CF_HIP_CHECK(ctx, hipMemcpy(sum_sq, p.out + blocks, sizeof(double), hipMemcpyDeviceToHost));
     return CF_OK;
@@ -851,9 +537,9 @@ extern "C" int cf_als_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* use
     if (blocks > 0x7fffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_als_predict: too many pairs");
     PairLayout p{};
     CF_TRY(upload_pairs(ctx, p, n_pairs, user, item, nullptr, n_users, n_items, D, U, V, n_pairs));
-    hipLaunchKernelGGL(als_predict_kernel, dim3((unsigned)blocks), dim3(kAT), 0, nullptr, n_pairs,
+    hipLaunchKernelGGL(mf_predict_kernel, dim3((unsigned)blocks), dim3(kAT), 0, nullptr, n_pairs,
                        (const uint32_t*)p.user, (const uint32_t*)p.item, (const double*)p.U, (const double*)p.V, (int)D,
-                       p.out);
+                       (const double*)nullptr, (const double*)nullptr, 0.0, 0, 0.0, 0.0, p.out);
     CF_HIP_CHECK(ctx, hipGetLastError());
     CF_HIP_CHECK(ctx, hipMemcpy(pred, p.out, sizeof(double) * n_pairs, hipMemcpyDeviceToHost));
     return CF_OK;

@@ -169,9 +169,12 @@ struct cf_ctx {
     // graph filter (cf_graph_filter): device time of the last call's supersteps, its edges
     float filter_ms = 0.0f;
     uint64_t filter_nnz = 0;
-    // ALS (cf_als.hip): one workspace holding everything a call needs, sized before its first launch
+    // ALS and SGD (cf_als.hip, cf_sgd.hip): one workspace holding everything a call needs, sized
+    // before its first launch
     void* d_als = nullptr;
     size_t als_bytes = 0;
+    // SGD (cf_sgd_timing): device time of the last fit's reduction kernels, user side and item side
+    float sgd_reduce_ms[2] = {0.0f, 0.0f};
 };
 
 // One launch of the eigen / predict kernels covers the users of one k-bucket.

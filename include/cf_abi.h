@@ -30,6 +30,9 @@
  *                                  knn3.cpp:185-256
  *   cf_als_fit / _error / _predict : als_vertex_program, error_aggregator and prediction_saver,
  *                                  als.cpp:290-371,424-510
+ *   cf_sgd_fit / _error / _predict : sgd_vertex_program / biassgd_vertex_program with their
+ *                                  error_aggregator and prediction_saver, sgd.cpp:243-339,344-425
+ *                                  and biassgd.cpp:249-347,399-434
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -63,7 +66,7 @@ int cf_device_count(void);
 int cf_create(int device, cf_ctx** out);
 void cf_destroy(cf_ctx* ctx);
 /* Waits for the context's device, then frees its cached HBM workspaces (eigen and predictor
- * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS); each is
+ * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD); each is
  * allocated again, at the size its next call plans, when that call runs.  The spill paths
  * size their workspaces from the device's free HBM, so a workspace the predictor left behind
  * shrinks the next eigen call's and costs it waves: call this between stages of a long-lived
@@ -533,6 +536,68 @@ int cf_als_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const ui
  * at most low_max edges take one wave. */
 int cf_debug_als_segment(void);
 int cf_debug_als_low_max(void);
+
+/* ---- SGD and bias-SGD matrix factorization (sgd.cpp, biassgd.cpp; synchronous engine, --interval 0)
+ * The graph, the six CSR arrays and their checks are those of cf_als_fit.  State: U, V (fp64), for
+ * bias-SGD also bias_user, bias_item and params->global_mean (both bias pointers NULL = plain SGD:
+ * mean and biases are absent; exactly one NULL is CF_EINVAL), nupdates per vertex, and the step
+ * gamma, which starts at params->gamma.
+ * User superstep (0, 2, ..) over the active users A (superstep 0: activate_user[u] != 0, NULL =
+ * every user), every value read as it was at the start of the superstep.  Per TRAIN edge (u, i),
+ * u in A:  p = clamp(mean + bu[u] + bi[i] + U_u . V_i, minval, maxval),  err = (float)(p - obs)
+ * (a NaN err counts in n_nan).  Then  U_u += -gamma (sum_e err_e V_i + deg lambda U_u),
+ * bu[u] += -gamma (sum_e err_e + deg lambda bu[u]),  nupdates[u] += 1  (a user without edges only
+ * gets the increment).  Item i is signalled iff it has an edge to some u in A and
+ * nupdates[i] < max_updates; its message is -gamma (sum err_e U_u + cnt lambda V_i) over its cnt
+ * edges with u in A and fabs(err_e) > tol (bias: -gamma (sum err_e + cnt lambda bi[i])); a
+ * signalled item without such an edge receives zero.  lambda is applied in closed form (deg, cnt
+ * times at once), not per edge.  Then gamma *= step_dec (repeated multiplication).
+ * Item superstep (1, 3, ..): every signalled item adds its message, nupdates[i] += 1, and the
+ * next A is the users with an edge to a signalled item and nupdates[u] < max_updates.
+ * The run ends when the next set is empty, after max_supersteps supersteps (0 = no cap; a run cut
+ * after a user superstep drops the pending messages), or after a user superstep with n_nan > 0.
+ * The reference never stops without a cap (its scatter signals whatever tol is), so
+ * max_updates == UINT64_MAX with max_supersteps == 0 is CF_EINVAL.
+ * trace (may be NULL): row t < trace_rows receives {sum sq err over TRAIN, over the n_validate
+ * VALIDATE edges} right after user superstep t (new U, old V: the moment of the reference's
+ * per-iteration RMSE line), by the reduction of cf_sgd_error.
+ * Every summation order depends on the vertex's own degree only and there is no floating-point
+ * atomic: a repeated fit gives the same bits, and a user's new row does not depend on which other
+ * users are active.  Against the reference (thread-dependent orders) parity is to rounding. */
+typedef struct cf_sgd_params {
+    double lambda, gamma, step_dec, tol, minval, maxval, global_mean;
+    uint64_t max_updates;     /* UINT64_MAX = no cap */
+    uint32_t max_supersteps;  /* 0 = no cap */
+} cf_sgd_params;
+typedef struct cf_sgd_stats {
+    uint32_t supersteps;   /* supersteps run */
+    uint64_t updates;      /* vertex updates executed */
+    uint64_t messages;     /* edges with |err| > tol that sent a message */
+    uint64_t n_nan;        /* NaN errors met (the reference dies on the first) */
+    double gamma_next;     /* the step the next user superstep would use */
+    float reduce_ms;       /* device time of the reduction kernels, both sides (HIP events) */
+    float apply_ms;        /* device time of the commit, signalling and compaction kernels */
+} cf_sgd_stats;
+int cf_sgd_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+               const uint32_t* user_item, const float* user_obs, const uint64_t* item_off,
+               const uint32_t* item_user, const float* item_obs, const cf_sgd_params* params, double* U, double* V,
+               double* bias_user, double* bias_item, uint32_t* nupdates_user, uint32_t* nupdates_item,
+               const uint8_t* activate_user, uint64_t n_validate, const uint32_t* val_user, const uint32_t* val_item,
+               const float* val_obs, double* trace, uint32_t trace_rows, cf_sgd_stats* stats);
+/* Device time of the last cf_sgd_fit's reduction kernels per side (their sum is reduce_ms). */
+int cf_sgd_timing(cf_ctx* ctx, float* user_reduce_ms, float* item_reduce_ms);
+/* extract_l2_error summed over the edges of one role (sgd.cpp:393-401, biassgd.cpp:399-409):
+ * *sum_sq = sum (obs - clamp(mean + bu + bi + u.v, minval, maxval))^2.  With NULL biases the mean
+ * is ignored and the sum is cf_als_error's, bit for bit (the same kernels). */
+int cf_sgd_error(cf_ctx* ctx, uint64_t n_edges, const uint32_t* user, const uint32_t* item, const float* obs,
+                 uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
+                 const double* bias_user, const double* bias_item, double global_mean, double minval, double maxval,
+                 double* sum_sq);
+/* prediction_saver::save_edge: sgd.cpp:413-424 is unclamped (clamp = 0), biassgd.cpp:418-433
+ * clamps (clamp != 0). */
+int cf_sgd_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const uint32_t* item, uint32_t n_users,
+                   uint32_t n_items, uint32_t D, const double* U, const double* V, const double* bias_user,
+                   const double* bias_item, double global_mean, int clamp, double minval, double maxval, double* pred);
 
 #ifdef __cplusplus
 }
