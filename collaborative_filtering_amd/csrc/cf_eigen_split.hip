@@ -40,6 +40,7 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kRoleActive = 1u << 31;
 constexpr uint32_t kTrWrite = 1u << 31;
 constexpr uint32_t kTrRead = 1u << 30;
+constexpr int kTrFLShift = 16;      // device table only: FL of the level in bits 16-23 of a trans word
 
 constexpr int split_ld(int nr) {   // smallest LD >= nr with LD == 16 or 48 (mod 64): conflict-free
     int ld = nr;
@@ -518,6 +519,10 @@ const std::vector<uint32_t>& host_table(int* kmax_ok) {
             for (int L = 0; L < kMaxLev; ++L) t[G::OFF_FL + L] = (uint32_t)S.FL[L];
             std::copy(S.role.begin(), S.role.end(), t + G::OFF_ROLE);
             std::copy(S.trans.begin(), S.trans.end(), t + G::OFF_TR);
+            // every trans word also carries its level's step count, so that the kernel fetches a
+            // level's words with one address and no scalar load
+            for (int L = 0; L < kMaxLev; ++L)
+                for (int g = 0; g < G::NG; ++g) t[G::OFF_TR + L * G::NG + g] |= (uint32_t)S.FL[L] << kTrFLShift;
             std::copy(S.end_g.begin(), S.end_g.end(), t + G::OFF_ENDG);
             std::copy(S.end_s.begin(), S.end_s.end(), t + G::OFF_ENDS);
         }
@@ -536,6 +541,8 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
     using G = SplitGeom<EMAX>;
     constexpr int NR = G::NR, E2 = G::E2, NG = G::NG, NT = G::NT, NS = G::NS, LD = G::LD;
     constexpr int NW = NT / 64;
+    constexpr int TW = (G::KHI + 63) / 64;   // 64-lane passes over a row or column of the slot
+    constexpr int JU = 8;                    // elements read ahead in the thread-per-row loops
     extern __shared__ float smem[];
     float* Bs = smem;
     float* s_nrm = Bs + (size_t)NS * LD;   // traveling columns: tracked squared norm, drift (by slot)
@@ -581,6 +588,10 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
     // W rows go to the slot and, RB at a time, through LDS (the slot area, LDT = k | 1: a thread
     // per row reads its row conflict-free) for the degree and sig_min passes
     const int LDT = k | 1;
+    const uint32_t kk1 = (uint32_t)(k * k - 1);   // the last element of the slot's k x k
+    // a loaded value pinned where it stands: the compiler otherwise sinks a load into the guarded
+    // store that uses it, behind a branch and a wait of its own
+    auto pin = [](float& x) { asm volatile("" : "+v"(x)); };
     const int RB = (NS * LD) / LDT;
     float* tile = Bs;
     for (int r0 = 0; r0 < k; r0 += RB) {
@@ -624,7 +635,17 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
         for (int i = r0 + tid; i < r0 + rb; i += NT) {
             const float* wr = tile + (i - r0) * LDT;
             double d = 0.0;
-            for (int j = 0; j < k; ++j) d += (double)wr[j];
+            // j in order, JU LDS reads in flight ahead of their adds (one read, one wait and one add
+            // per turn leaves the LDS latency of every element exposed)
+            int j = 0;
+            for (; j + JU <= k; j += JU) {
+                float x[JU];
+#pragma unroll
+                for (int q = 0; q < JU; ++q) x[q] = wr[j + q];
+#pragma unroll
+                for (int q = 0; q < JU; ++q) d += (double)x[q];
+            }
+            for (; j < k; ++j) d += (double)wr[j];
             if (d == 0.0) d = 1.0;                       // (:137-140)
             const double s = sqrt(1.0 / d);              // (:149-153)
             s_s[i] = (float)s;
@@ -636,18 +657,49 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
     for (int r0 = 0; r0 < k; r0 += RB) {
         const int rb = min(RB, k - r0);
         if (r0 > 0 || rb < k) {   // a single block is still in LDS
-            for (int idx = tid; idx < rb * k; idx += NT) {
-                const int i = idx / k, j = idx - i * k;
-                tile[i * LDT + j] = hb[(size_t)(r0 + i) * k + j];
+            // four rows per wave at a time, lanes along the row: 4 * TW loads in flight before the
+            // first LDS store.  The loads are unconditional, from offsets clamped into the slot (a
+            // guarded load is a branch with a wait of its own); the stores carry the bounds.
+            for (int i0 = 4 * wave; i0 < rb; i0 += 4 * NW) {
+                float w[4][TW];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int t = 0; t < TW; ++t) w[q][t] = hb[min((uint32_t)((r0 + i0 + q) * k + 64 * t + lane), kk1)];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int t = 0; t < TW; ++t) pin(w[q][t]);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int t = 0; t < TW; ++t) {
+                        const int i = i0 + q, j = 64 * t + lane;
+                        if (i < rb && j < k) tile[i * LDT + j] = w[q][t];
+                    }
             }
             __syncthreads();
         }
         for (int i = r0 + tid; i < r0 + rb; i += NT) {
             const float* wr = tile + (i - r0) * LDT;
-            const float si = s_s[i];
+            const float si = s_s[i], l2d = s_l2d[i];
             float acc = 0.0f;
-            for (int j = 0; j < k; ++j) {
-                const float l2 = (j == i) ? s_l2d[i] : -(si * wr[j]) * s_s[j];
+            int j = 0;
+            for (; j + JU <= k; j += JU) {   // j in order, the reads of JU elements ahead (stage 2a)
+                float x[JU], sj[JU];
+#pragma unroll
+                for (int q = 0; q < JU; ++q) {
+                    x[q] = wr[j + q];
+                    sj[q] = s_s[j + q];
+                }
+#pragma unroll
+                for (int q = 0; q < JU; ++q) {
+                    const float l2 = (j + q == i) ? l2d : -(si * x[q]) * sj[q];
+                    acc = fmaf(l2, l2, acc);
+                }
+            }
+            for (; j < k; ++j) {
+                const float l2 = (j == i) ? l2d : -(si * wr[j]) * s_s[j];
                 acc = fmaf(l2, l2, acc);
             }
             const float sg = (float)((double)sqrtf(acc) + 0.01);   // (:172-176, :182)
@@ -665,16 +717,46 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
         for (int c0 = 0; c0 < k; c0 += G::CB) {
             const int cb = min(G::CB, k - c0);
             // r > c: W(r, c), lanes over the block's columns (a row segment per pass)
-            for (int idx = tid; idx < (k - c0) * G::CB; idx += NT) {
-                const int r = c0 + idx / G::CB, cc = idx % G::CB, c = c0 + cc;
-                if (cc < cb && c < r) tile[cc * LDT + r] = -(s_s[r] * hb[(size_t)r * k + c]) * s_s[c];
+            // Both passes load several iterations' elements into registers before the tile stores,
+            // unconditionally from offsets clamped into the slot; `c < r` selects at the store.
+            const int na = (k - c0) * G::CB;
+            for (int idx0 = tid; idx0 < na; idx0 += 4 * NT) {
+                float v[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int idx = idx0 + q * NT;
+                    v[q] = hb[min((uint32_t)((c0 + idx / G::CB) * k + c0 + idx % G::CB), kk1)];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pin(v[q]);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int idx = idx0 + q * NT;
+                    const int r = c0 + idx / G::CB, cc = idx % G::CB, c = c0 + cc;
+                    if (idx < na && cc < cb && c < r) tile[cc * LDT + r] = -(s_s[r] * v[q]) * s_s[c];
+                }
             }
-            // r < c: W(c, r), a wave per column, lanes down its row of W; the diagonal
-            for (int cc = wave; cc < cb; cc += NW) {
-                const int c = c0 + cc;
-                const float* wr = hb + (size_t)c * k;
-                for (int r = lane; r < c; r += 64) tile[cc * LDT + r] = -(s_s[c] * wr[r]) * s_s[r];
-                if (lane == 0) tile[cc * LDT + c] = s_l2d[c] + 1.0f;
+            // r < c: W(c, r), a wave per column (four columns at a time), lanes down its row of W;
+            // the diagonal
+            for (int cc0 = wave; cc0 < cb; cc0 += 4 * NW) {
+                float v[4][TW];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int t = 0; t < TW; ++t)
+                        v[q][t] = hb[min((uint32_t)((c0 + cc0 + q * NW) * k + 64 * t + lane), kk1)];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int cc = cc0 + q * NW, c = c0 + cc;
+                    if (cc < cb) {
+#pragma unroll
+                        for (int t = 0; t < TW; ++t) {
+                            const int r = 64 * t + lane;
+                            if (r < c) tile[cc * LDT + r] = -(s_s[c] * v[q][t]) * s_s[r];
+                        }
+                        if (lane == 0) tile[cc * LDT + c] = s_l2d[c] + 1.0f;
+                    }
+                }
             }
             __syncthreads();
             for (int cc = wave; cc < cb; cc += NW) {
@@ -711,13 +793,16 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
     const float close2 = uni(refine ? a.close_sigrot * a.close_sigrot * tol * tol : stop2);
     const float dclose2 = uni(refine ? 2.0f * a.refine_delta * a.refine_delta : -1.0f);
     // column c of B in the slot, rows 16e + 2lig, +1 of this lane (zero past k)
+    // Unconditional loads, so that all of a column's loads are in flight at once (a guarded load is
+    // a branch with a wait of its own).  Rows below 16 (EMAX - 1) < KLO <= k exist for every k of the
+    // bucket; the last chunk loads from row indices clamped into the column and selects zero past k.
     auto load_col = [&](int c, f2* x) {
         const float* src = hb + (size_t)c * k;
 #pragma unroll
-        for (int e = 0; e < E2; ++e) {
-            const int r = 16 * e + 2 * lig;
-            x[e] = f2{r < k ? src[r] : 0.0f, r + 1 < k ? src[r + 1] : 0.0f};
-        }
+        for (int e = 0; e < E2 - 1; ++e) x[e] = f2{src[16 * e + 2 * lig], src[16 * e + 2 * lig + 1]};
+        const int r = 16 * (E2 - 1) + 2 * lig;
+        const float x0 = src[min(r, k - 1)], x1 = src[min(r + 1, k - 1)];
+        x[E2 - 1] = f2{r < k ? x0 : 0.0f, r + 1 < k ? x1 : 0.0f};
     };
     int sweep = 0;
     int steps_sweep = 0;
@@ -745,37 +830,44 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
             for (int j = tid; j < k; j += NT) s_map[j] = j;
         }
         __syncthreads();
-        // level 0: traveling rank f0 + x in slot x, then fixed F[g] = rank g in registers
-        if (g < k - f0) {
-            const int c = s_map[f0 + g];
-            const float* src = hb + (size_t)c * k;
-            f2* dst = reinterpret_cast<f2*>(Bs + (size_t)g * LD);
-#pragma unroll
-            for (int e = 0; e < E2; ++e) {
-                const int r = 16 * e + 2 * lig;
-                lds_st(dst + kGroup * e + lig, f2{r < k ? src[r] : 0.0f, r + 1 < k ? src[r + 1] : 0.0f});
-            }
-            if (lig == 0) {
-                s_nrm[g] = s_cn[c];
-                s_dev[g] = s_cd[c];
-            }
-        }
+        // level 0: traveling rank f0 + x in slot x, fixed F[g] = rank g in registers.  Both columns'
+        // loads stand before the first LDS store, each column's in flight together.  A
+        // group without a traveling (fixed) column loads its fixed (any) one again and drops it.
         f2 xp[E2];
         float devp = 0.0f, al = 0.0f;
-        if (g < f0) {
-            const int c = s_map[g];
-            load_col(c, xp);
-            devp = s_cd[c];
-        } else {
+        {
+            const bool trav = g < k - f0, fixd = g < f0;
+            static_assert(NG < G::KLO, "s_map[g] is a column for every group");
+            const int ct = s_map[trav ? f0 + g : g];
+            const int cf = s_map[g];
+            f2 xt[E2];
+            load_col(ct, xt);
+            load_col(cf, xp);
+            if (trav) {
+                f2* dst = reinterpret_cast<f2*>(Bs + (size_t)g * LD);
 #pragma unroll
-            for (int e = 0; e < E2; ++e) xp[e] = f2{0.f, 0.f};
+                for (int e = 0; e < E2; ++e) lds_st(dst + kGroup * e + lig, xt[e]);
+                if (lig == 0) {
+                    s_nrm[g] = s_cn[ct];
+                    s_dev[g] = s_cd[ct];
+                }
+            }
+            if (fixd) {
+                devp = s_cd[cf];
+            } else {
+#pragma unroll
+                for (int e = 0; e < E2; ++e) xp[e] = f2{0.f, 0.f};
+            }
         }
         __syncthreads();
         for (int L = 0; L < nlev; ++L) {
+            // The level's trans and role words load together (the trans word carries the level's step
+            // count): one wait on the schedule table per level, and role's passes behind the moves.
+            const uint32_t tr = tab[G::OFF_TR + L * NG + g];
+            const uint32_t role = tab[G::OFF_ROLE + L * NG + g];
             if (L > 0) {
                 // level change: write this group's column to slot X and/or read slot Y (a swap
                 // when X == Y: every lane reads its rows before it writes them)
-                const uint32_t tr = tab[G::OFF_TR + L * NG + g];
                 if (tr & (kTrRead | kTrWrite)) {
                     const bool rd = tr & kTrRead, wr = tr & kTrWrite;
                     const f2* src = reinterpret_cast<const f2*>(Bs + (size_t)((tr >> 8) & 0xFF) * LD);
@@ -801,8 +893,7 @@ __global__ __launch_bounds__(SplitGeom<EMAX>::NT, SplitGeom<EMAX>::WPE) void spl
                 }
                 __syncthreads();
             }
-            const uint32_t role = tab[G::OFF_ROLE + L * NG + g];
-            const int FL = (int)tab[G::OFF_FL + L];
+            const int FL = __builtin_amdgcn_readfirstlane((tr >> kTrFLShift) & 0xFF);
             const bool active = role & kRoleActive;
             const int fi = role & 0xFF, P = (role >> 8) & 0xFF, t = (role >> 16) & 0xFF, bsl = (role >> 24) & 0x7F;
             if (active) {   // fresh norm of the fixed column at every level start
