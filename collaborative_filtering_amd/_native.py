@@ -129,6 +129,13 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "cf_sgd_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_double, c_int, c_double, c_double, c_void_p]),
+    "cf_svdpp_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_uint32, c_void_p]),
+    "cf_svdpp_timing": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_svdpp_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "cf_debug_als_segment": (c_int, []),
     "cf_debug_als_low_max": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
@@ -168,7 +175,24 @@ class SgdStats(ctypes.Structure):
                 ("gamma_next", c_double), ("reduce_ms", c_float), ("apply_ms", c_float)]
 
 
-EIGEN_SINK = ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))
+class SvdppParams(ctypes.Structure):
+    """cf_svdpp_params (cf_abi.h)."""
+    _fields_ = [(k, c_float) for k in ("user_bias_step", "user_bias_reg", "item_bias_step", "item_bias_reg",
+                                       "user_factor_step", "user_factor_reg", "item_factor_step", "item_factor_reg",
+                                       "item_factor2_step", "item_factor2_reg")] + \
+               [("step_dec", c_double), ("minval", c_double), ("maxval", c_double), ("global_mean", c_double),
+                ("max_updates", c_uint64), ("max_supersteps", c_uint32)]
+
+
+class SvdppStats(ctypes.Structure):
+    """cf_svdpp_stats (cf_abi.h)."""
+    _fields_ = [("supersteps", c_uint32), ("updates", c_uint64), ("messages", c_uint64), ("n_nan", c_uint64),
+                ("user_bias_step", c_float), ("item_bias_step", c_float), ("user_factor_step", c_float),
+                ("item_factor_step", c_float), ("item_factor2_step", c_float), ("reduce_ms", c_float),
+                ("apply_ms", c_float)]
+
+
+EIGEN_SINK =ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))
 
 _lib = None
 

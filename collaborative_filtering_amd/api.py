@@ -108,6 +108,40 @@ class SgdResult:
         return self.nupdates_user, self.nupdates_item
 
 
+@dataclass
+class SvdppResult:
+    """Outcome of Context.svdpp_fit: the four fitted matrices (U, W per user; V, Y per item), the
+    biases, per-vertex update counts, the trace (one row {sum sq err TRAIN, sum sq err VALIDATE}
+    per user superstep of either phase, without Y) and the cf_svdpp_stats of the run; steps_next
+    holds the five steps the next user superstep would use (user_bias, item_bias, user_factor,
+    item_factor, item_factor2); the three *_reduce_ms split reduce_ms by kernel kind."""
+
+    U: np.ndarray
+    V: np.ndarray
+    W: np.ndarray
+    Y: np.ndarray
+    bias_user: np.ndarray
+    bias_item: np.ndarray
+    nupdates_user: np.ndarray
+    nupdates_item: np.ndarray
+    trace: np.ndarray
+    global_mean: float
+    supersteps: int
+    updates: int
+    messages: int
+    n_nan: int
+    steps_next: np.ndarray
+    reduce_ms: float
+    apply_ms: float
+    phase1_reduce_ms: float
+    user_reduce_ms: float
+    item_reduce_ms: float
+
+    @property
+    def nupdates(self):
+        return self.nupdates_user, self.nupdates_item
+
+
 def _csr(row, col, obs, n_rows):
     """Stable CSR of an edge list by row (edges of one row keep their input order)."""
     perm = np.argsort(row, kind="stable")
@@ -686,6 +720,116 @@ class Context:
         self._chk(self.lib.cf_sgd_predict(self.h, len(user), ptr(user), ptr(item), U.shape[0], V.shape[0], U.shape[1],
                                           ptr(U), ptr(V), ptr(bu), ptr(bi), float(global_mean), int(bool(clamp)),
                                           float(minval), float(maxval), ptr(pred)), "cf_sgd_predict")
+        return pred
+
+    # -- SVD++ matrix factorization (svdpp.cpp) ---------------------------------------------
+    def svdpp_fit(self, user, item, obs, n_users, n_items, U0, V0, W0, Y0, *, implicit=None, user_bias_step=1e-4,
+                  user_bias_reg=1e-4, item_bias_step=1e-4, item_bias_reg=1e-4, user_factor_step=1e-4,
+                  user_factor_reg=1e-4, item_factor_step=1e-4, item_factor_reg=1e-4, item_factor2_step=1e-4,
+                  item_factor2_reg=1e-4, step_dec=0.9, minval=-1e100, maxval=1e100, global_mean=None, bias_user=None,
+                  bias_item=None, max_updates=None, max_supersteps=0, activate_user=None, nupdates=None,
+                  validate=None, trace=True) -> "SvdppResult":
+        """cf_svdpp_fit over the TRAIN edges (user[e], item[e], obs[e]) from the initial U0, W0
+        (n_users x D) and V0, Y0 (n_items x D).  implicit: optional (user, item) pairs of the
+        non-TRAIN edges (VALIDATE and PREDICT), which enter W_u and the phase-1 signalling.  The
+        ten hyper-parameters are rounded to float32 (svdpp.cpp:49-58).  Biases start at bias_user /
+        bias_item (None: zeros); global_mean defaults to the fp64 mean of the TRAIN ratings.  One
+        of max_updates / max_supersteps is mandatory; max_updates counts phase-1 and phase-2
+        updates alike.  validate, nupdates, activate_user: as sgd_fit."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        n_users, n_items = int(n_users), int(n_items)
+        mats = [np.array(x, dtype=np.float64, order="C") for x in (U0, V0, W0, Y0)]
+        ns = (n_users, n_items, n_users, n_items)
+        dims = {a.size // n for a, n in zip(mats, ns) if n}
+        if len(dims) > 1:
+            raise ValueError("U0, V0, W0 and Y0 differ in D")
+        D = dims.pop() if dims else (mats[0].shape[1] if mats[0].ndim == 2 and mats[0].shape[1] else 1)
+        if any(a.size != n * D for a, n in zip(mats, ns)):
+            raise ValueError("U0 / W0 / V0 / Y0 do not hold n_users x D / n_items x D values")
+        U, V, W, Y = (a.reshape(n, D) for a, n in zip(mats, ns))
+        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
+            raise ValueError("edge index out of range")
+        uoff, uitem, uobs = _csr(user, item, obs, n_users)
+        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        poff = pitem = None
+        if implicit is not None and len(implicit[0]):
+            pu = np.ascontiguousarray(implicit[0], dtype=np.uint32)
+            pi = np.ascontiguousarray(implicit[1], dtype=np.uint32)
+            if int(pu.max()) >= n_users:
+                raise ValueError("implicit user index out of range")
+            poff, pitem, _ = _csr(pu, pi, np.zeros(len(pu), np.float32), n_users)
+        bu = np.zeros(n_users) if bias_user is None else np.array(bias_user, dtype=np.float64)
+        bi = np.zeros(n_items) if bias_item is None else np.array(bias_item, dtype=np.float64)
+        if global_mean is None:
+            mean = float(obs.astype(np.float64).sum() / len(obs)) if len(obs) else 0.0
+        else:
+            mean = float(global_mean)
+        act = None if activate_user is None else np.ascontiguousarray(np.asarray(activate_user) != 0, dtype=np.uint8)
+        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
+            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        cap = (1 << 64) - 1 if max_updates is None else int(max_updates)
+        max_supersteps = int(max_supersteps)
+        rows = 0
+        if trace:   # one row per user superstep, bounded by whichever cap is set
+            bounds = [(max_supersteps + 1) // 2] if max_supersteps else []
+            if max_updates is not None:
+                bounds.append(int(max_updates) + 1)
+            rows = min(bounds) if bounds else 0
+        tr = np.zeros((max(rows, 1), 2))
+        vu = vi = vo = None
+        if validate is not None and len(validate[0]):
+            vu = np.ascontiguousarray(validate[0], dtype=np.uint32)
+            vi = np.ascontiguousarray(validate[1], dtype=np.uint32)
+            vo = np.ascontiguousarray(validate[2], dtype=np.float32)
+        par = _native.SvdppParams(user_bias_step, user_bias_reg, item_bias_step, item_bias_reg, user_factor_step,
+                                  user_factor_reg, item_factor_step, item_factor_reg, item_factor2_step,
+                                  item_factor2_reg, float(step_dec), float(minval), float(maxval), mean, cap,
+                                  max_supersteps)
+        st = _native.SvdppStats()
+        self._chk(self.lib.cf_svdpp_fit(self.h, n_users, n_items, int(D), ptr(uoff), ptr(uitem), ptr(uobs), ptr(ioff),
+                                        ptr(iuser), ptr(iobs), ptr(poff), ptr(pitem), byref(par), ptr(U), ptr(V),
+                                        ptr(W), ptr(Y), ptr(bu), ptr(bi), ptr(nu[0]), ptr(nu[1]), ptr(act),
+                                        0 if vu is None else len(vu), ptr(vu), ptr(vi), ptr(vo),
+                                        ptr(tr) if rows else None, rows, byref(st)), "cf_svdpp_fit")
+        ms = [c_float(), c_float(), c_float()]
+        self._chk(self.lib.cf_svdpp_timing(self.h, byref(ms[0]), byref(ms[1]), byref(ms[2])), "cf_svdpp_timing")
+        done = min(rows, (int(st.supersteps) + 1) // 2)
+        steps = np.array([st.user_bias_step, st.item_bias_step, st.user_factor_step, st.item_factor_step,
+                          st.item_factor2_step], dtype=np.float32)
+        return SvdppResult(U, V, W, Y, bu, bi, nu[0], nu[1], tr[:done].copy(), mean, int(st.supersteps),
+                           int(st.updates), int(st.messages), int(st.n_nan), steps, float(st.reduce_ms),
+                           float(st.apply_ms), float(ms[0].value), float(ms[1].value), float(ms[2].value))
+
+    def svdpp_sum_sq_error(self, user, item, obs, U, V, bias_user, bias_item, global_mean=0.0, minval=-1e100,
+                           maxval=1e100) -> float:
+        """The reference's SVD++ error (extract_l2_error, svdpp.cpp:466-476) leaves Y out: it is
+        cf_sgd_error with the biases."""
+        return self.sgd_sum_sq_error(user, item, obs, U, V, bias_user, bias_item, global_mean, minval, maxval)
+
+    def svdpp_rmse(self, user, item, obs, U, V, bias_user, bias_item, global_mean=0.0, minval=-1e100,
+                   maxval=1e100) -> float:
+        """RMSE of one role's edges (error_aggregator::finalize, svdpp.cpp:440-453)."""
+        return self.sgd_rmse(user, item, obs, U, V, bias_user, bias_item, global_mean, minval, maxval)
+
+    def svdpp_predict(self, user, item, U, V, Y, bias_user, bias_item, global_mean=0.0, minval=-1e100,
+                      maxval=1e100) -> np.ndarray:
+        """cf_svdpp_predict per (user, item) pair: clamp(mean + bu + bi + U_u . (V_i + Y_i)), always
+        clamped (svdpp.cpp:490-493)."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        bu = np.ascontiguousarray(bias_user, dtype=np.float64)
+        bi = np.ascontiguousarray(bias_item, dtype=np.float64)
+        if Y.shape != V.shape:
+            raise ValueError("Y and V differ in shape")
+        pred = np.zeros(len(user), dtype=np.float64)
+        self._chk(self.lib.cf_svdpp_predict(self.h, len(user), ptr(user), ptr(item), U.shape[0], V.shape[0],
+                                            U.shape[1], ptr(U), ptr(V), ptr(Y), ptr(bu), ptr(bi), float(global_mean),
+                                            float(minval), float(maxval), ptr(pred)), "cf_svdpp_predict")
         return pred
 
     # -- device-resident paths (torch CUDA tensors) -------------------------------

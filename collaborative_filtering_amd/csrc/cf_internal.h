@@ -175,6 +175,9 @@ struct cf_ctx {
     size_t als_bytes = 0;
     // SGD (cf_sgd_timing): device time of the last fit's reduction kernels, user side and item side
     float sgd_reduce_ms[2] = {0.0f, 0.0f};
+    // SVD++ (cf_svdpp_timing): the same of the last cf_svdpp_fit per kernel kind: phase-1 user
+    // reduction, phase-2 user reduction, item message reduction
+    float svdpp_reduce_ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
 // One launch of the eigen / predict kernels covers the users of one k-bucket.

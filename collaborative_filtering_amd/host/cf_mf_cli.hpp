@@ -1,7 +1,7 @@
-// cf_mf_cli.hpp -- what the matrix-factorization drop-ins (bin_als, bin_sgd, bin_biassgd) share:
-// the three-role movielens/ loader with the fatal range check, the TRAIN CSRs, the reproducible
-// initial factors, the writers of P, P.U and P.V, and sgd_main(), all of bin_sgd and bin_biassgd
-// but the switch between them.
+// cf_mf_cli.hpp -- what the matrix-factorization drop-ins (bin_als, bin_sgd, bin_biassgd,
+// bin_svdpp) share: the three-role movielens/ loader with the fatal range check, the TRAIN CSRs,
+// the reproducible initial factors, the writers of P, P.U and P.V, sgd_main(), all of bin_sgd and
+// bin_biassgd but the switch between them, and svdpp_main(), all of bin_svdpp.
 // Initial factors: the reference draws them with Eigen's setRandom() (als.cpp:103, sgd.cpp:104),
 // i.e. the C library's rand() stream in vertex-construction order, which is not reproducible.
 // Here factor d of the vertex with compact index i on side s (0 users, 1 items; compact = rank
@@ -314,6 +314,129 @@ inline int sgd_main(int argc, char** argv, bool bias) {
             write_vertex_values(data.uids, predictions + ".bias.U", nshards, bu, 1, " ", false);
             write_vertex_values(data.mids, predictions + ".bias.V", nshards, bi, 1, " ", false);
         }
+    }
+    cf_destroy(ctx);
+    return 0;
+}
+
+// svdpp: drop-in for svdpp.cpp.
+//   svdpp.cpp:587-610   loader (as als.cpp's); the .validate and .predict edges are the implicit list
+//   svdpp.cpp:268-397   vertex program on the synchronous engine (cf_svdpp_fit)
+//   svdpp.cpp:412-476   error aggregate, one line per user superstep of either phase (the trace)
+//   svdpp.cpp:479-578,790-807   --predictions P: P, P.U, P.V, P.bias.U, P.bias.V (the weights are not saved)
+//   svdpp.cpp:664-697   options; --lambda, --gamma and --tol are parsed and never used there: accepted, ignored
+// Deviations: those of sgd_main; the biases start at 0 (the reference never initialises them).
+// Initial values: pvec is init_factors(seed, side) as for sgd; weight is the same draw with the
+// side numbers 2 (users, W) and 3 (items, Y), so the four matrices are independent streams.
+// --max_iter counts phase-1 and phase-2 updates alike: --max_iter 2k gives k gradient passes.
+inline int svdpp_main(int argc, char** argv) {
+    const std::string dir = matrix_dir(argc, argv);
+    const uint32_t D = (uint32_t)std::stoul(cfcli::opt(argc, argv, "D", "20"));
+    const std::string max_iter = cfcli::opt(argc, argv, "max_iter", "");
+    cf_svdpp_params par{};
+    par.max_updates = max_iter.empty() ? std::numeric_limits<uint64_t>::max() : std::stoull(max_iter);
+    par.user_bias_step = std::stof(cfcli::opt(argc, argv, "user_bias_step", "1e-4"));
+    par.user_bias_reg = std::stof(cfcli::opt(argc, argv, "user_bias_reg", "1e-4"));
+    par.item_bias_step = std::stof(cfcli::opt(argc, argv, "item_bias_step", "1e-4"));
+    par.item_bias_reg = std::stof(cfcli::opt(argc, argv, "item_bias_reg", "1e-4"));
+    par.user_factor_step = std::stof(cfcli::opt(argc, argv, "user_factor_step", "1e-4"));
+    par.user_factor_reg = std::stof(cfcli::opt(argc, argv, "user_factor_reg", "1e-4"));
+    par.item_factor_step = std::stof(cfcli::opt(argc, argv, "item_factor_step", "1e-4"));
+    par.item_factor_reg = std::stof(cfcli::opt(argc, argv, "item_factor_reg", "1e-4"));
+    par.item_factor2_step = std::stof(cfcli::opt(argc, argv, "item_factor2_step", "1e-4"));
+    par.item_factor2_reg = std::stof(cfcli::opt(argc, argv, "item_factor2_reg", "1e-4"));
+    par.step_dec = std::stod(cfcli::opt(argc, argv, "step_dec", "0.9"));
+    par.maxval = std::stod(cfcli::opt(argc, argv, "maxval", "1e+100"));
+    par.minval = std::stod(cfcli::opt(argc, argv, "minval", "-1e+100"));
+    par.max_supersteps = (uint32_t)std::stoul(cfcli::opt(argc, argv, "max_supersteps", "0"));
+    const std::string predictions = cfcli::opt(argc, argv, "predictions", "");
+    const uint64_t seed = std::stoull(cfcli::opt(argc, argv, "seed", "0"));
+    const int nshards = std::stoi(cfcli::opt(argc, argv, "nshards", "4"));
+    if (std::stoul(cfcli::opt(argc, argv, "interval", "0")) != 0)
+        cfcli::die("--interval other than 0 is not supported (it ties the step decay to wall-clock time)");
+    if (std::stoi(cfcli::opt(argc, argv, "implicitratingtype", "0")) != 0)
+        cfcli::die("--implicitratingtype other than 0 (implicit.hpp's added edges) is not supported");
+    if (D == 0 || D > CF_ALS_MAX_D) cfcli::die("--D must be between 1 and " + std::to_string(CF_ALS_MAX_D));
+    if (max_iter.empty() && par.max_supersteps == 0)
+        cfcli::die("--max_iter or --max_supersteps is required (without a cap the run never ends)");
+
+    const Data data = load(dir, par.minval, par.maxval);
+    const uint32_t nu = data.nu, nm = data.nm;
+    const auto& eu = data.eu;
+    const auto& em = data.em;
+    const auto& eo = data.eo;
+    {   // svdpp.cpp:758-761
+        double sum = 0.0;
+        for (float o : eo[cfio::kTrain]) sum += (double)o;
+        par.global_mean = eo[cfio::kTrain].empty() ? 0.0 : sum / (double)eo[cfio::kTrain].size();
+        std::string line = "Global mean is: ";
+        cfio::append_g(line, par.global_mean);
+        std::printf("%s\n", line.c_str());
+    }
+    // the implicit list: the VALIDATE edges, then the PREDICT edges, by user
+    std::vector<uint32_t> iu(eu[1]), im(em[1]);
+    iu.insert(iu.end(), eu[2].begin(), eu[2].end());
+    im.insert(im.end(), em[2].begin(), em[2].end());
+    const Csr imp = build_csr(nu, iu, im, std::vector<float>(iu.size(), 0.0f));
+    std::vector<double> U, V, W, Y, bu(nu, 0.0), bi(nm, 0.0);
+    init_factors(U, nu, D, seed, 0);
+    init_factors(V, nm, D, seed, 1);
+    init_factors(W, nu, D, seed, 2);
+    init_factors(Y, nm, D, seed, 3);
+    std::vector<uint32_t> nup_u(nu, 0), nup_m(nm, 0);
+    uint64_t rows = par.max_supersteps ? (par.max_supersteps + 1) / 2 : std::numeric_limits<uint64_t>::max();
+    if (!max_iter.empty()) rows = std::min<uint64_t>(rows, par.max_updates + 1);
+    if (rows > (1u << 24)) cfcli::die("more than 2^24 user supersteps asked for");
+    std::vector<double> trace(2 * (size_t)rows, 0.0);
+
+    cf_ctx* ctx = cfcli::open_device();
+    std::printf("Running SVD++\n");
+    std::printf("Time   Training    Validation\n       RMSE        RMSE \n");
+    cf_svdpp_stats st{};
+    const auto t0 = std::chrono::steady_clock::now();
+    cfcli::check(ctx,
+                 cf_svdpp_fit(ctx, nu, nm, D, data.by_user.off.data(), data.by_user.nbr.data(), data.by_user.obs.data(),
+                              data.by_item.off.data(), data.by_item.nbr.data(), data.by_item.obs.data(), imp.off.data(),
+                              imp.nbr.data(), &par, U.data(), V.data(), W.data(), Y.data(), bu.data(), bi.data(),
+                              nup_u.data(), nup_m.data(), nullptr, eu[1].size(), eu[1].data(), em[1].data(), eo[1].data(),
+                              trace.data(), (uint32_t)rows, &st),
+                 "cf_svdpp_fit");
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const uint32_t done = (st.supersteps + 1) / 2;
+    for (uint32_t t = 0; t < done && t < rows; ++t)
+        print_iteration(wall * (t + 1) / done, eu[0].empty() ? 0.0 : std::sqrt(trace[2 * t] / (double)eu[0].size()),
+                        !eu[1].empty(), eu[1].empty() ? 0.0 : std::sqrt(trace[2 * t + 1] / (double)eu[1].size()));
+    if (st.n_nan)   // svdpp.cpp:294-295
+        cfcli::die("Got into numeric errors.. try to tune step size and regularization using command line flags");
+    std::printf("----------------------------------------------------------\n");
+    std::printf("Supersteps: %u  reduction kernels: %.3f ms  apply kernels: %.3f ms\n", st.supersteps, st.reduce_ms,
+                st.apply_ms);
+    std::printf("Updates executed: %llu\n", (unsigned long long)st.updates);
+    std::printf("Messages sent: %llu\n", (unsigned long long)st.messages);
+    std::printf("Final error: \n");
+    double sq[2] = {0.0, 0.0};
+    for (int role = 0; role < 2; ++role)   // extract_l2_error: without Y
+        cfcli::check(ctx,
+                     cf_sgd_error(ctx, eu[role].size(), eu[role].data(), em[role].data(), eo[role].data(), nu, nm, D,
+                                  U.data(), V.data(), bu.data(), bi.data(), par.global_mean, par.minval, par.maxval,
+                                  &sq[role]),
+                     "cf_sgd_error");
+    std::printf("%s\n", rmse_line(data, sq).c_str());
+
+    if (!predictions.empty()) {
+        std::printf("Saving predictions\n");
+        const size_t np = eu[cfio::kPredict].size();
+        std::vector<double> pred(np);
+        cfcli::check(ctx,
+                     cf_svdpp_predict(ctx, np, eu[cfio::kPredict].data(), em[cfio::kPredict].data(), nu, nm, D, U.data(),
+                                      V.data(), Y.data(), bu.data(), bi.data(), par.global_mean, par.minval, par.maxval,
+                                      pred.data()),
+                     "cf_svdpp_predict");
+        write_predictions(data, predictions, nshards, pred);
+        write_vertex_values(data.uids, predictions + ".U", nshards, U, D, " ", true);   // svdpp.cpp:509-512: "id f0 f1 .. "
+        write_vertex_values(data.mids, predictions + ".V", nshards, V, D, " ", true);
+        write_vertex_values(data.uids, predictions + ".bias.U", nshards, bu, 1, " ", false);
+        write_vertex_values(data.mids, predictions + ".bias.V", nshards, bi, 1, " ", false);
     }
     cf_destroy(ctx);
     return 0;

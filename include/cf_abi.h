@@ -33,6 +33,8 @@
  *   cf_sgd_fit / _error / _predict : sgd_vertex_program / biassgd_vertex_program with their
  *                                  error_aggregator and prediction_saver, sgd.cpp:243-339,344-425
  *                                  and biassgd.cpp:249-347,399-434
+ *   cf_svdpp_fit / _predict        : svdpp_vertex_program and prediction_saver, svdpp.cpp:268-397,
+ *                                  479-499 (its error_aggregator is cf_sgd_error)
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -66,7 +68,7 @@ int cf_device_count(void);
 int cf_create(int device, cf_ctx** out);
 void cf_destroy(cf_ctx* ctx);
 /* Waits for the context's device, then frees its cached HBM workspaces (eigen and predictor
- * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD); each is
+ * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD / SVD++); each is
  * allocated again, at the size its next call plans, when that call runs.  The spill paths
  * size their workspaces from the device's free HBM, so a workspace the predictor left behind
  * shrinks the next eigen call's and costs it waves: call this between stages of a long-lived
@@ -598,6 +600,84 @@ int cf_sgd_error(cf_ctx* ctx, uint64_t n_edges, const uint32_t* user, const uint
 int cf_sgd_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const uint32_t* item, uint32_t n_users,
                    uint32_t n_items, uint32_t D, const double* U, const double* V, const double* bias_user,
                    const double* bias_item, double global_mean, int clamp, double minval, double maxval, double* pred);
+
+/* ---- SVD++ matrix factorization (svdpp.cpp:268-397,412-499; synchronous engine, --interval 0)
+ * The graph, the six TRAIN CSR arrays and their checks are those of cf_sgd_fit.  imp_off / imp_item
+ * is a CSR by user over the non-TRAIN edges (VALIDATE and PREDICT; imp_off NULL = none, item indices
+ * are bound-checked).  deg_all(u) = TRAIN degree + implicit degree (num_out_edges: every role) and
+ * usrNorm_u = (float)(1 / sqrt(deg_all(u))).
+ * State: per user U_u (pvec), W_u (weight), bu, nupdates; per item V_i (pvec), Y_i (weight), bi,
+ * nupdates; the five steps {user,item}_bias_step, {user,item}_factor_step, item_factor2_step, which
+ * are floats and start at the params' values; the regularisers are floats too.  --lambda, --gamma
+ * and --tol of the reference are never used and have no field here.
+ * The phase of a vertex is the parity of its OWN nupdates: even = phase 1, odd = phase 2; vertices
+ * of both phases can run in the same superstep.
+ * User superstep (0, 2, ..) over the active users A (superstep 0: activate_user[u] != 0, NULL =
+ * every user), every value read as it was at the start of the superstep:
+ *   u in phase 1:  W_u = usrNorm_u * sum Y_i over EVERY edge of u (TRAIN first, then the implicit
+ *     list; a user without any edge keeps W_u); every neighbour item of any role is signalled
+ *     without the max_updates check; U_u and bu do not change.
+ *   u in phase 2, per TRAIN edge (u, i):
+ *     p = clamp(mean + bu[u] + bi[i] + U_u . (V_i + Y_i), minval, maxval)   (the ITEM's weight)
+ *     err = (float)(obs - p)          (sign opposite to cf_sgd_fit; a NaN err counts in n_nan)
+ *     U_u  += sum user_factor_step * err * (V_i - user_factor_reg * U_u)
+ *     bu[u] += sum user_bias_step * err       (user_bias_reg multiplies a local 0 in the reference)
+ *     and, iff nupdates[i] < max_updates, item i receives, summed over its senders,
+ *       dV  = item_factor_step * (err * (U_u + W_u) - item_factor_reg * V_i)
+ *       dbi = item_bias_step * err             (item_bias_reg: as user_bias_reg)
+ *       dY  = err * V_i * (float)(item_factor2_step * usrNorm_u)
+ *             - (double)(float)(item_factor2_step * item_factor2_reg) * Y_i
+ *     and every TRAIN item with nupdates < max_updates is signalled (a signal carries zero).
+ *     A non-TRAIN edge contributes nothing.  A phase-2 user without a TRAIN edge is unchanged.
+ *   Either way nupdates[u] += 1.  The regulariser sums are applied in closed form (once per vertex:
+ *   reg * own * sum err on the user side, cnt * reg * own on the item side), not per edge.
+ *   Then each of the five steps becomes (float)(step * step_dec).
+ * Item superstep (1, 3, ..): every signalled item, in phase 1 discards its messages, in phase 2
+ * adds them (V_i += sum dV, Y_i += sum dY, bi += sum dbi); nupdates[i] += 1; the next A is the
+ * users of its TRAIN edges with nupdates[u] < max_updates.
+ * The run ends when the next set is empty, after max_supersteps supersteps (0 = no cap; a run cut
+ * after a user superstep drops the pending messages), or after a user superstep with n_nan > 0.
+ * max_updates counts phase-1 and phase-2 updates alike.  The reference never stops without a cap:
+ * max_updates == UINT64_MAX with max_supersteps == 0 is CF_EINVAL.
+ * trace (may be NULL): row t < trace_rows receives {sum sq err over TRAIN, over the n_validate
+ * VALIDATE edges} right after user superstep t of either phase, by the reduction of cf_sgd_error:
+ * extract_l2_error (svdpp.cpp:466-476) is mean + bu + bi + U_u . V_i clamped, WITHOUT Y.
+ * The reference leaves vertex_data::bias uninitialised (svdpp.cpp:87-89); here the biases are
+ * inputs.  Determinism is that of cf_sgd_fit: a vertex's degree class, split points and summation
+ * orders depend on its own degree only (the all-role degree in phase 1, the TRAIN degree elsewhere),
+ * no floating-point atomics; an edge's err has the same float bits on the user and the item side. */
+typedef struct cf_svdpp_params {
+    float user_bias_step, user_bias_reg, item_bias_step, item_bias_reg, user_factor_step, user_factor_reg,
+        item_factor_step, item_factor_reg, item_factor2_step, item_factor2_reg;
+    double step_dec, minval, maxval, global_mean;
+    uint64_t max_updates;     /* UINT64_MAX = no cap */
+    uint32_t max_supersteps;  /* 0 = no cap */
+} cf_svdpp_params;
+typedef struct cf_svdpp_stats {
+    uint32_t supersteps;   /* supersteps run */
+    uint64_t updates;      /* vertex updates executed, of either phase */
+    uint64_t messages;     /* TRAIN edges of phase-2 users that sent a message to a phase-2 item */
+    uint64_t n_nan;        /* NaN errors met on TRAIN edges (the reference dies on the first) */
+    /* the steps the next user superstep would use */
+    float user_bias_step, item_bias_step, user_factor_step, item_factor_step, item_factor2_step;
+    float reduce_ms;       /* device time of the three reduction kernel kinds (HIP events) */
+    float apply_ms;        /* device time of the commit, signalling and compaction kernels */
+} cf_svdpp_stats;
+int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+                 const uint32_t* user_item, const float* user_obs, const uint64_t* item_off,
+                 const uint32_t* item_user, const float* item_obs, const uint64_t* imp_off, const uint32_t* imp_item,
+                 const cf_svdpp_params* params, double* U, double* V, double* W, double* Y, double* bias_user,
+                 double* bias_item, uint32_t* nupdates_user, uint32_t* nupdates_item, const uint8_t* activate_user,
+                 uint64_t n_validate, const uint32_t* val_user, const uint32_t* val_item, const float* val_obs,
+                 double* trace, uint32_t trace_rows, cf_svdpp_stats* stats);
+/* Device time of the last cf_svdpp_fit per kernel kind (their sum is reduce_ms). */
+int cf_svdpp_timing(cf_ctx* ctx, float* phase1_reduce_ms, float* user_reduce_ms, float* item_reduce_ms);
+/* prediction_saver::save_edge (svdpp.cpp:490-493): clamp(mean + bu + bi + U_u . (V_i + Y_i)); always
+ * clamped.  The training error is cf_sgd_error (no Y), so there is no cf_svdpp_error. */
+int cf_svdpp_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const uint32_t* item, uint32_t n_users,
+                     uint32_t n_items, uint32_t D, const double* U, const double* V, const double* Y,
+                     const double* bias_user, const double* bias_item, double global_mean, double minval,
+                     double maxval, double* pred);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,280 @@
+"""SVD++ matrix factorization on the GPU (cf_svdpp_fit / cf_svdpp_predict, the trace by
+cf_sgd_error's reduction) against the numpy checker tests/svdpp_ref.py.
+
+The cases' schedules do not depend on any rounding (the phase is the parity of an integer) and
+every error is at least 1e-6 float ulps away from a float midpoint (test_svdpp_ref.py), so update
+counts, supersteps and message counts are compared exactly.  Factor and bias bound: BOUND = 1e-12
+* max|factor| after every superstep -- 100 times the checker's own drift under permuted edge lists
+and initial matrices perturbed by 1e-15 relative (2.0e-15, measured in test_svdpp_ref.py), rounded
+up to a power of ten.  The device shows at most 9.3e-16 of max|factor| on the four cases and 2.3e-15 on
+the segmented problem (the figures every test prints)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import sgd_ref as sr
+import svdpp_ref as pr
+from collaborative_filtering_amd import _native
+from collaborative_filtering_amd._native import ptr
+from test_svdpp_ref import BOUND
+
+pytestmark = pytest.mark.gpu
+
+_FITS = {}
+U64_MAX = (1 << 64) - 1
+NAMES6 = ("U", "V", "W", "Y", "bu", "bi")
+
+
+def device_fit(ctx, name, *, case=None, **over):
+    c = pr.case_inputs(name) if case is None else case
+    g = c.g
+    kw = dict(pr.HYPER, implicit=(c.imp_user, c.imp_item), max_updates=c.max_updates, activate_user=g.out_degree > 0,
+              validate=(g.vuser, g.vitem, g.vobs))
+    kw.update(over)
+    return ctx.svdpp_fit(g.user, g.item, g.obs, g.n_users, g.n_items, c.U0, c.V0, c.W0, c.Y0, **kw)
+
+
+def case_fit(ctx, name):
+    """The device's run of a case, computed once and shared (not modified by the tests)."""
+    if name not in _FITS:
+        _FITS[name] = device_fit(ctx, name)
+    return _FITS[name]
+
+
+def state(r):
+    return r.U, r.V, r.W, r.Y, r.bias_user, r.bias_item
+
+
+def assert_state(tag, r, snap):
+    scale = max(np.max(np.abs(snap[k])) for k in range(4))
+    worst = 0.0
+    for nm, got, want in zip(NAMES6, state(r), snap[:6]):
+        err = float(np.max(np.abs(got - want))) if want.size else 0.0
+        worst = max(worst, err / scale)
+        assert err <= BOUND * scale, (tag, nm, err, scale)
+    print(tag, "max|d| / max|factor|", worst)
+    assert np.array_equal(r.nupdates_user, snap[6]) and np.array_equal(r.nupdates_item, snap[7]), tag
+    return worst
+
+
+@pytest.mark.parametrize("name", pr.NAMES)
+def test_case_matches_checker(gpu_ctx, name):
+    c = pr.case_inputs(name)
+    ref = pr.case_reference(name)
+    low = _native.load().cf_debug_als_low_max()
+    deg = np.bincount(c.g.item, minlength=c.g.n_items)
+    assert deg.max() > low >= deg[deg > 0].min()   # both wave and workgroup paths
+    r = case_fit(gpu_ctx, name)
+    print(name, "supersteps", r.supersteps, ref.supersteps, "updates", r.updates, ref.updates, "messages", r.messages,
+          ref.messages)
+    assert r.supersteps == ref.supersteps and r.updates == ref.updates and r.messages == ref.messages and r.n_nan == 0
+    assert r.steps_next.tobytes() == ref.steps_next.tobytes()
+    assert r.global_mean == sr.train_mean(c.g.obs)
+    assert_state(f"{name} final", r, ref.snapshots[-1])
+    for s in range(1, ref.supersteps):   # after every superstep: the run cut there
+        cut = device_fit(gpu_ctx, name, max_supersteps=s)
+        assert cut.supersteps == s
+        assert_state(f"{name} s={s}", cut, ref.snapshots[s - 1])
+        steps = np.array([pr.HYPER[k] for k in pr.STEP_NAMES], np.float32)
+        for _ in range((s + 1) // 2):   # one decay per user superstep of either phase
+            steps = (steps.astype(np.float64) * pr.HYPER["step_dec"]).astype(np.float32)
+        assert cut.steps_next.tobytes() == steps.tobytes()
+
+
+def by_user(u, i, o):
+    p = np.argsort(u, kind="stable")
+    return u[p], i[p], o[p]
+
+
+@pytest.mark.parametrize("name", pr.NAMES)
+def test_trace_and_predictions(gpu_ctx, name):
+    c = pr.case_inputs(name)
+    g = c.g
+    ref = pr.case_reference(name)
+    r = case_fit(gpu_ctx, name)
+    want = np.array(ref.trace)
+    mean = r.global_mean
+    assert r.trace.shape == want.shape == (ref.supersteps // 2, 2)
+    tu, ti, to = by_user(g.user, g.item, g.obs)   # the fit reduces the TRAIN edges in its CSR order
+    for t in range(len(want)):
+        cut = device_fit(gpu_ctx, name, max_supersteps=2 * t + 1)
+        for col, (u, i, o) in enumerate(((tu, ti, to), (g.vuser, g.vitem, g.vobs))):
+            got = gpu_ctx.svdpp_sum_sq_error(u, i, o, cut.U, cut.V, cut.bias_user, cut.bias_item, mean, 1.0, 5.0)
+            assert np.float64(cut.trace[t, col]).tobytes() == np.float64(got).tobytes()   # cf_sgd_error, bit for bit
+            assert cut.trace[t, col] == r.trace[t, col]                                     # the full run's row
+            assert abs(cut.trace[t, col] - want[t, col]) <= 1e-12 * want[t, col]            # the checker's (no Y)
+    assert abs(gpu_ctx.svdpp_rmse(tu, ti, to, r.U, r.V, r.bias_user, r.bias_item, mean, 1.0, 5.0)
+               - np.sqrt(sr.sum_sq_error(tu, ti, to, r.U, r.V, r.bias_user, r.bias_item, mean, 1.0, 5.0) / len(tu))) <= 1e-12
+    rng = np.random.default_rng(3)
+    pu = rng.integers(0, g.n_users, 50).astype(np.uint32)
+    pi = rng.integers(0, g.n_items, 50).astype(np.uint32)
+    got = gpu_ctx.svdpp_predict(pu, pi, r.U, r.V, r.Y, r.bias_user, r.bias_item, mean, 1.0, 5.0)
+    raw = mean + r.bias_user[pu] + r.bias_item[pi] + np.einsum("ij,ij->i", r.U[pu], r.V[pi] + r.Y[pi])
+    scale = abs(mean) + np.abs(r.bias_user[pu]) + np.abs(r.bias_item[pi]) + np.abs(r.U[pu] * (r.V[pi] + r.Y[pi])).sum(axis=1)
+    assert np.any(np.clip(raw, 1.0, 5.0) != raw) and np.all((got >= 1.0) & (got <= 5.0))   # always clamped
+    assert np.all(np.abs(got - np.clip(raw, 1.0, 5.0)) <= BOUND * scale)
+    assert np.array_equal(np.clip(raw, 1.0, 5.0), pr.predict(pu, pi, r.U, r.V, r.Y, r.bias_user, r.bias_item, mean, 1.0, 5.0))
+    without_y = gpu_ctx.sgd_predict(pu, pi, r.U, r.V, r.bias_user, r.bias_item, mean, minval=1.0, maxval=5.0)
+    assert np.any(without_y != got)
+
+
+def test_repeat_is_bit_identical(gpu_ctx):
+    a, b = case_fit(gpu_ctx, "A"), device_fit(gpu_ctx, "A")
+    for x, y in zip(state(a) + (a.nupdates_user, a.nupdates_item, a.trace), state(b) + (b.nupdates_user, b.nupdates_item, b.trace)):
+        assert x.tobytes() == y.tobytes()
+    assert a.messages == b.messages
+
+
+def test_independent_of_the_active_set(gpu_ctx):
+    c = pr.case_inputs("A")
+    g = c.g
+    even = (np.arange(g.n_users) % 2 == 0) & (g.out_degree > 0)
+    # superstep 0 (phase 1): W_u of an active user does not depend on who else is active
+    full = device_fit(gpu_ctx, "A", max_supersteps=1)
+    part = device_fit(gpu_ctx, "A", max_supersteps=1, activate_user=even)
+    assert part.W[even].tobytes() == full.W[even].tobytes() and not np.array_equal(full.W[even], c.W0[even])
+    assert np.array_equal(part.W[~even], c.W0[~even])
+    assert not np.any(part.nupdates_user[~even]) and np.all(part.nupdates_user[even] == 1)
+    # superstep 2 (phase 2): its inputs U, bu, V, Y, bi are still the initial ones in both runs
+    full = device_fit(gpu_ctx, "A", max_supersteps=3)
+    part = device_fit(gpu_ctx, "A", max_supersteps=3, activate_user=even)
+    assert part.U[even].tobytes() == full.U[even].tobytes() and part.bias_user[even].tobytes() == full.bias_user[even].tobytes()
+    assert not np.array_equal(full.U[even], c.U0[even])
+    # the mixed-phase supersteps (2 and 4: even users one phase ahead of the odd ones) against the checker
+    ref = pr.run_case("A", activate_user=even, max_supersteps=6)
+    assert ref.mixed_supersteps == 2 and ref.discarded > 0
+    for s in (3, 5, 6):
+        got = device_fit(gpu_ctx, "A", activate_user=even, max_supersteps=s)
+        assert got.supersteps == s
+        assert_state(f"subset s={s}", got, ref.snapshots[s - 1])
+    assert got.messages == ref.messages and got.updates == ref.updates
+
+
+def test_segmented_vertex(gpu_ctx):
+    """Item 0 is rated by segment + 52 users (two segment partials in HBM), item 1 and user 0 are
+    above the low cut on the TRAIN list (one workgroup each), user 1 is above it on its all-role
+    list only (phase 1 takes the workgroup path, phase 2 one wave), everything else takes one wave."""
+    lib = _native.load()
+    user, item, obs, nu, ni, iu, ii, (U0, V0, W0, Y0) = pr.segmented_case(lib.cf_debug_als_segment(),
+                                                                          lib.cf_debug_als_low_max())
+    low = lib.cf_debug_als_low_max()
+    du = np.bincount(user, minlength=nu)
+    assert du[1] <= low < du[1] + np.sum(iu == 1)
+    hyper = dict(pr.HYPER)
+    for k in pr.STEP_NAMES:   # an item with thousands of raters: small steps
+        hyper[k] = pr.HYPER[k] * 0.1
+    mean = sr.train_mean(obs)
+    ref = pr.fit(user, item, obs, nu, ni, U0, V0, W0, Y0, implicit=(iu, ii), mean=mean, max_updates=2,
+                 keep_snapshots=True, **hyper)
+    assert ref.supersteps == 4 and ref.round_margin >= 1e-6 and ref.messages == len(user) and ref.max_change > 1e-3
+    runs = [gpu_ctx.svdpp_fit(user, item, obs, nu, ni, U0, V0, W0, Y0, implicit=(iu, ii), max_updates=2, **hyper)
+            for _ in range(2)]
+    r = runs[0]
+    assert r.supersteps == 4 and r.messages == ref.messages and r.updates == ref.updates and r.n_nan == 0
+    assert_state("segmented", r, ref.snapshots[-1])
+    one = gpu_ctx.svdpp_fit(user, item, obs, nu, ni, U0, V0, W0, Y0, implicit=(iu, ii), max_supersteps=1, **hyper)
+    assert_state("segmented s=1", one, ref.snapshots[0])
+    for x, y in zip(state(r), state(runs[1])):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_caps(gpu_ctx):
+    c = pr.case_inputs("A")
+    two = device_fit(gpu_ctx, "A", max_updates=2)
+    ref = pr.run_case("A", max_updates=2)
+    assert two.supersteps == ref.supersteps == 4 and two.updates == ref.updates
+    assert two.nupdates_user.max() == 2 and two.nupdates_item.max() == 2
+    assert_state("max_updates=2", two, ref.snapshots[-1])
+    one = device_fit(gpu_ctx, "A", max_updates=1)   # an odd cap: phase 1 alone, nothing but W and the counts move
+    ref1 = pr.run_case("A", max_updates=1)
+    assert one.supersteps == ref1.supersteps == 2 and one.messages == 0
+    assert_state("max_updates=1", one, ref1.snapshots[-1])
+    assert np.array_equal(one.U, c.U0) and np.array_equal(one.V, c.V0) and np.array_equal(one.Y, c.Y0)
+    odd = device_fit(gpu_ctx, "A", max_supersteps=3)   # the pending messages are dropped
+    assert odd.supersteps == 3 and odd.messages > 0 and odd.trace.shape == (2, 2)
+    assert np.array_equal(odd.V, c.V0) and np.array_equal(odd.Y, c.Y0) and not np.any(odd.bias_item)
+    assert not np.array_equal(odd.U, c.U0) and odd.nupdates_item.max() == 1
+    assert one.nupdates_user[0] == 0 and np.array_equal(one.W[0], c.W0[0])     # no edges at all: never signalled
+    assert one.nupdates_user[2] == 1 and not np.array_equal(one.W[2], c.W0[2])  # VALIDATE only: phase 1 reaches it
+    assert one.nupdates_item[-1] == 0
+
+
+def raw_fit(ctx, n_users, n_items, D, uoff, uitem, ioff, iuser, max_updates=4, max_supersteps=0, poff=None, pitem=None):
+    nnz = len(uitem)
+    obs = np.ones(max(nnz, 1), np.float32)
+    z = lambda n, t: np.zeros(max(n, 1), t)   # noqa: E731
+    mats = [np.zeros((max(n, 1), D)) for n in (n_users, n_items, n_users, n_items)]
+    par = _native.SvdppParams(*([0.02, 0.05] * 5), 0.9, 1.0, 5.0, 3.0, max_updates, max_supersteps)
+    st = _native.SvdppStats()
+    rc = ctx.lib.cf_svdpp_fit(ctx.h, n_users, n_items, D, ptr(uoff), ptr(uitem), ptr(obs), ptr(ioff), ptr(iuser),
+                              ptr(obs), ptr(poff), ptr(pitem), ctypes.byref(par), *[ptr(m) for m in mats],
+                              ptr(z(n_users, np.float64)), ptr(z(n_items, np.float64)), ptr(z(n_users, np.uint32)),
+                              ptr(z(n_items, np.uint32)), None, 0, None, None, None, None, 0, ctypes.byref(st))
+    return rc, st
+
+
+def test_argument_checks_and_empty_inputs(gpu_ctx):
+    u64, u32 = np.uint64, np.uint32
+    uoff, uitem = np.array([0, 1, 2], u64), np.array([0, 0], u32)
+    ioff, iuser = np.array([0, 2], u64), np.array([0, 1], u32)
+    rc, st = raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser)   # imp_off == NULL
+    assert rc == _native.CF_OK and st.supersteps == 8 and st.updates == 12 and st.messages == 4
+    rc, st = raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser, poff=np.array([0, 0, 1], u64), pitem=np.array([0], u32))
+    assert rc == _native.CF_OK and st.supersteps == 8
+    assert raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser, max_updates=U64_MAX)[0] == _native.CF_EINVAL   # no cap
+    assert raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser, max_updates=U64_MAX, max_supersteps=3)[0] == _native.CF_OK
+    assert raw_fit(gpu_ctx, 2, 1, 65, uoff, uitem, ioff, iuser)[0] == _native.CF_ERANGE
+    assert raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, np.array([0, 1], u64), iuser)[0] == _native.CF_EINVAL   # edge totals differ
+    assert raw_fit(gpu_ctx, 2, 2, 4, uoff, uitem, np.array([0, 1, 2], u64), iuser)[0] == _native.CF_EINVAL   # per-item counts
+    assert raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser, poff=np.array([0, 0, 1], u64),
+                   pitem=np.array([1], u32))[0] == _native.CF_EINVAL   # implicit item out of range
+    assert raw_fit(gpu_ctx, 2, 1, 4, uoff, uitem, ioff, iuser, poff=np.array([0, 2, 1], u64),
+                   pitem=np.array([0, 0], u32))[0] == _native.CF_EINVAL   # implicit offsets decrease
+    rc, st = raw_fit(gpu_ctx, 0, 0, 4, np.zeros(1, u64), np.zeros(0, u32), np.zeros(1, u64), np.zeros(0, u32))
+    assert rc == _native.CF_OK and st.supersteps == 0 and st.updates == 0 and st.user_factor_step == np.float32(0.02)
+    rc, st = raw_fit(gpu_ctx, 2, 1, 4, np.zeros(3, u64), np.zeros(0, u32), np.zeros(2, u64), np.zeros(0, u32))   # no edges
+    assert rc == _native.CF_OK and st.supersteps == 1 and st.updates == 2 and st.messages == 0
+    rc, st = raw_fit(gpu_ctx, 2, 0, 4, np.zeros(3, u64), np.zeros(0, u32), np.zeros(1, u64), np.zeros(0, u32))   # no items
+    assert rc == _native.CF_OK and st.supersteps == 1 and st.updates == 2
+    # implicit edges alone: phase 1 signals the item, the item signals nobody
+    rc, st = raw_fit(gpu_ctx, 2, 1, 4, np.zeros(3, u64), np.zeros(0, u32), np.zeros(2, u64), np.zeros(0, u32),
+                     poff=np.array([0, 1, 1], u64), pitem=np.array([0], u32))
+    assert rc == _native.CF_OK and st.supersteps == 2 and st.updates == 3
+
+
+def test_python_layer_accepts_an_empty_side(gpu_ctx):
+    e = np.zeros((0, 4))
+    r = gpu_ctx.svdpp_fit([], [], [], 0, 0, e, e, e, e, max_updates=2)
+    assert r.supersteps == 0 and r.updates == 0 and r.U.shape == (0, 4) and r.trace.shape == (0, 2)
+    with pytest.raises(_native.NativeError):
+        gpu_ctx.svdpp_fit([0], [0], [3.0], 1, 1, np.ones((1, 2)), np.ones((1, 2)), np.ones((1, 2)), np.ones((1, 2)))   # no cap
+
+
+def test_nan_stops_the_fit(gpu_ctx):
+    c = pr.case_inputs("A")
+    g = c.g
+    V0 = c.V0.copy()
+    V0[0, 3] = np.nan   # item 0: a TRAIN edge of every user with TRAIN edges
+    r = gpu_ctx.svdpp_fit(g.user, g.item, g.obs, g.n_users, g.n_items, c.U0, V0, c.W0, c.Y0, implicit=(c.imp_user, c.imp_item),
+                          max_supersteps=8, activate_user=g.out_degree > 0, **pr.HYPER)
+    # supersteps 0 and 1 are phase 1 (no error is computed); the NaN shows in the user superstep 2
+    assert r.n_nan == int(np.sum(g.item == 0)) and r.supersteps == 3
+    assert np.array_equal(r.V[1:], V0[1:]) and np.array_equal(r.Y, c.Y0)   # the messages were never applied
+
+
+def test_workspace_release_and_sgd_unchanged(gpu_ctx):
+    """SVD++ carves the context's matrix-factorization workspace: released, then allocated again;
+    cf_sgd_fit gives the same bytes before and after an SVD++ fit on the same context."""
+    g, U0, V0, mu = sr.case_inputs("A")
+    kw = dict(sr.HYPER, bias=True, max_updates=mu, activate_user=g.out_degree > 0, validate=(g.vuser, g.vitem, g.vobs))
+    before = gpu_ctx.sgd_fit(g.user, g.item, g.obs, g.n_users, g.n_items, U0, V0, **kw)
+    a = device_fit(gpu_ctx, "C")
+    after = gpu_ctx.sgd_fit(g.user, g.item, g.obs, g.n_users, g.n_items, U0, V0, **kw)
+    for x, y in ((before.U, after.U), (before.V, after.V), (before.bias_user, after.bias_user),
+                 (before.bias_item, after.bias_item), (before.trace, after.trace)):
+        assert x.tobytes() == y.tobytes()
+    gpu_ctx.release_workspaces()
+    b = device_fit(gpu_ctx, "C")
+    for x, y in zip(state(a), state(b)):
+        assert x.tobytes() == y.tobytes()
