@@ -16,6 +16,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "libcf_host.so")
 CF_OK = 0
 CF_EINVAL = -1
 CF_ERANGE = -4
+CF_SVD_MAX_NV = 256
 CF_ALS_MAX_D = 64
 CF_SIGS_OWN = 0
 CF_SIGS_COMPAT = 1
@@ -136,6 +137,12 @@ SIGNATURES = {
     "cf_svdpp_timing": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "cf_svdpp_predict": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
+    "cf_svd_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_uint32, c_uint32, c_uint32, c_double, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_svd_matvec": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_debug_svd_wave_max": (c_int, []),
+    "cf_debug_small_svd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cf_debug_als_segment": (c_int, []),
     "cf_debug_als_low_max": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
@@ -190,6 +197,12 @@ class SvdppStats(ctypes.Structure):
                 ("user_bias_step", c_float), ("item_bias_step", c_float), ("user_factor_step", c_float),
                 ("item_factor_step", c_float), ("item_factor2_step", c_float), ("reduce_ms", c_float),
                 ("apply_ms", c_float)]
+
+
+class SvdStats(ctypes.Structure):
+    """cf_svd_stats (cf_abi.h)."""
+    _fields_ = [("nconv", c_uint32), ("passes", c_uint32), ("products", c_uint32), ("matvec_ms", c_float),
+                ("ortho_ms", c_float), ("rotate_ms", c_float)]
 
 
 EIGEN_SINK =ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))

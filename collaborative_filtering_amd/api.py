@@ -142,6 +142,29 @@ class SvdppResult:
         return self.nupdates_user, self.nupdates_item
 
 
+@dataclass
+class SvdResult:
+    """Outcome of Context.svd_fit: sigma and errest (nv entries; positions no pass reached are
+    NaN), err (the residual error of the min(nsv, nconv) reported triplets), U (rows x nsv) and V
+    (cols x nsv) with the reported triplets in their first columns, kk of every pass, the first
+    pass's alpha and beta, and the cf_svd_stats of the run."""
+
+    sigma: np.ndarray
+    errest: np.ndarray
+    err: np.ndarray
+    U: np.ndarray
+    V: np.ndarray
+    kk_pass: np.ndarray
+    alpha_first: np.ndarray
+    beta_first: np.ndarray
+    nconv: int
+    passes: int
+    products: int
+    matvec_ms: float
+    ortho_ms: float
+    rotate_ms: float
+
+
 def _csr(row, col, obs, n_rows):
     """Stable CSR of an edge list by row (edges of one row keep their input order)."""
     perm = np.argsort(row, kind="stable")
@@ -831,6 +854,68 @@ class Context:
                                             U.shape[1], ptr(U), ptr(V), ptr(Y), ptr(bu), ptr(bi), float(global_mean),
                                             float(minval), float(maxval), ptr(pred)), "cf_svdpp_predict")
         return pred
+
+    # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
+    @staticmethod
+    def svd_entries(row, col, val, rows, cols, regularization=0.0):
+        """The entries cf_svd_fit sees.  A square matrix keeps its diagonal apart in the reference
+        (A_ii, the last line of a vertex wins, svd.cpp:276-280) and adds --regularization to it
+        (math.hpp:137-138): here entry (i, i) = (float)(A_ii + regularization) wherever that is not
+        0.  For a non-square matrix the regularization is ignored, as there."""
+        row = np.ascontiguousarray(row, dtype=np.uint32)
+        col = np.ascontiguousarray(col, dtype=np.uint32)
+        val = np.ascontiguousarray(val, dtype=np.float32)
+        if int(rows) != int(cols):
+            return row, col, val
+        diag = np.zeros(int(rows), dtype=np.float64)
+        on = row == col
+        diag[row[on]] = val[on]   # the last one wins
+        diag += float(regularization)
+        keep = np.flatnonzero(diag != 0.0).astype(np.uint32)
+        return (np.concatenate([row[~on], keep]), np.concatenate([col[~on], keep]),
+                np.concatenate([val[~on], diag[keep].astype(np.float32)]))
+
+    def svd_fit(self, row, col, val, rows, cols, nsv, nv, max_iter=10, tol=1e-8, ortho_repeats=3, v0=None,
+                regularization=0.0, seed=0) -> "SvdResult":
+        """cf_svd_fit: the leading nsv singular triplets of the rows x cols matrix with entries
+        (row[e], col[e], val[e]) from nv Lanczos vectors per restart.  v0 (rows entries) is the
+        start vector; None draws it uniform in [0, 1) from `seed` (the reference: randu)."""
+        rows, cols, nsv, nv = int(rows), int(cols), int(nsv), int(nv)
+        row, col, val = self.svd_entries(row, col, val, rows, cols, regularization)
+        if len(row) and (int(row.max()) >= rows or int(col.max()) >= cols):
+            raise ValueError("entry index out of range")
+        roff, rcol, rval = _csr(row, col, val, rows)
+        coff, crow, cval = _csr(col, row, val, cols)
+        v0 = np.random.default_rng(seed).random(rows) if v0 is None else np.ascontiguousarray(v0, dtype=np.float64)
+        if v0.size != rows:
+            raise ValueError("v0 does not hold `rows` values")
+        sigma, errest = np.full(max(nv, 1), np.nan), np.full(max(nv, 1), np.nan)
+        err = np.full(max(nsv, 1), np.nan)
+        U = np.zeros((max(nsv, 1), rows), dtype=np.float64)   # column-major rows x nsv
+        V = np.zeros((max(nsv, 1), cols), dtype=np.float64)
+        kk = np.zeros(max(int(max_iter), 1), dtype=np.uint32)
+        ab = np.full(2 * max(nv, 1), np.nan)
+        st = _native.SvdStats()
+        self._chk(self.lib.cf_svd_fit(self.h, rows, cols, ptr(roff), ptr(rcol), ptr(rval), ptr(coff), ptr(crow),
+                                      ptr(cval), nsv, nv, int(max_iter), float(tol), int(ortho_repeats), ptr(v0),
+                                      ptr(sigma), ptr(errest), ptr(err), ptr(U), ptr(V), ptr(kk), ptr(ab), byref(st)),
+                  "cf_svd_fit")
+        return SvdResult(sigma[:nv], errest[:nv], err[:nsv], U[:nsv].T, V[:nsv].T, kk[:int(st.passes)].copy(),
+                         ab[:nv].copy(), ab[max(nv, 1):max(nv, 1) + nv].copy(), int(st.nconv), int(st.passes),
+                         int(st.products), float(st.matvec_ms), float(st.ortho_ms), float(st.rotate_ms))
+
+    def svd_matvec(self, off, nbr, val, n_out, n_in, x) -> np.ndarray:
+        """cf_svd_matvec: y = M x for the CSR (off, nbr, val) with n_out rows and n_in columns."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        nbr = np.ascontiguousarray(nbr, dtype=np.uint32)
+        val = np.ascontiguousarray(val, dtype=np.float32)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if len(off) != int(n_out) + 1 or x.size != int(n_in):
+            raise ValueError("off / x do not match n_out / n_in")
+        y = np.zeros(int(n_out), dtype=np.float64)
+        self._chk(self.lib.cf_svd_matvec(self.h, int(n_out), int(n_in), ptr(off), ptr(nbr), ptr(val), ptr(x), ptr(y)),
+                  "cf_svd_matvec")
+        return y
 
     # -- device-resident paths (torch CUDA tensors) -------------------------------
     def plan(self, item_off_host) -> "Plan":

@@ -35,6 +35,8 @@
  *                                  and biassgd.cpp:249-347,399-434
  *   cf_svdpp_fit / _predict        : svdpp_vertex_program and prediction_saver, svdpp.cpp:268-397,
  *                                  479-499 (its error_aggregator is cf_sgd_error)
+ *   cf_svd_fit / cf_svd_matvec     : lanczos() with Axb and orthogonalize_vs_all, svd.cpp:304-505,
+ *                                  math.hpp:98-185,805-906
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -68,7 +70,7 @@ int cf_device_count(void);
 int cf_create(int device, cf_ctx** out);
 void cf_destroy(cf_ctx* ctx);
 /* Waits for the context's device, then frees its cached HBM workspaces (eigen and predictor
- * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD / SVD++); each is
+ * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD / SVD++ / SVD); each is
  * allocated again, at the size its next call plans, when that call runs.  The spill paths
  * size their workspaces from the device's free HBM, so a workspace the predictor left behind
  * shrinks the next eigen call's and costs it waves: call this between stages of a long-lived
@@ -678,6 +680,61 @@ int cf_svdpp_predict(cf_ctx* ctx, uint64_t n_pairs, const uint32_t* user, const 
                      uint32_t n_items, uint32_t D, const double* U, const double* V, const double* Y,
                      const double* bias_user, const double* bias_item, double global_mean, double minval,
                      double maxval, double* pred);
+
+/* ---- truncated SVD of the rating matrix by restarted Golub-Kahan-Lanczos (svd.cpp:304-505) ----
+ * A is rows x cols, given as two CSRs of the same entries (row_* by row, col_* by column: u64
+ * offsets, u32 neighbour, f32 value; checked like cf_als_fit's).  U (rows x nsv) holds the left
+ * vectors, V (cols x nsv) the right ones, both column-major (vector i at U + i * rows).  The
+ * reference swaps the names inside lanczos(): its V[i] live on the rows and its U[i] on the columns.
+ * Below P[i] is row-side, Q[i] column-side, nv + 1 vectors each; fp64 throughout.
+ *   P[0] = v0 / |v0|, nconv = 0, its = 1; while nconv < nsv && its < max_iter (so at most
+ *   max_iter - 1 passes), with k = nconv:
+ *     Q[k] = A^T P[k], orthogonalised against Q[0..k), normalised: alpha[0]
+ *     for i = k+1 .. nv-1:  P[i] = A Q[i-1] against P[0..i): beta[i-k-1];
+ *                           Q[i] = A^T P[i] against Q[0..i): alpha[i-k]
+ *     P[nv] = A Q[nv-1] against P[0..nv): beta[nv-k-1]
+ *     m = nv - nconv; T = bidiag(alpha, beta[0..m-1)) = a diag(b) PT^T (host, one-sided Jacobi, b
+ *     descending); sigma[nconv+j] = b[j]; errest[nconv+j] = |a(m-1,j) beta[m-1]|, divided by b[j]
+ *     when b[j] > tol; kk = the number of new errest < tol; P[:, nconv..nconv+kk) = P[:, nconv..nv)
+ *     PT[:, 0..kk), Q likewise with a; done when nconv + kk >= nsv, else P[nconv+kk] = sum_t
+ *     PT(t, kk) P[nconv+t], nconv += kk, its++.
+ *   Orthogonalisation: classical Gram-Schmidt, ortho_repeats (1..3) times, all coefficients from the
+ *   same vector; the vector is divided by its norm only when the norm is >= 1e-10 (math.hpp:898).
+ *   Afterwards, for i < min(nsv, nconv): err[i] = sqrt(|A^T P[i] - sigma_i Q[i]|^2 + |A Q[i] -
+ *   sigma_i P[i]|^2), divided by sigma_i when sigma_i > tol.
+ * Outputs: sigma[nv], errest[nv] (positions a pass did not reach stay as passed in), err[nsv] and
+ * the first min(nsv, nconv) columns of U and V (the rest untouched); kk_pass (optional, max_iter
+ * entries) receives kk of every pass, first_ab (optional, 2 nv doubles) the first pass's alpha
+ * then beta.  A square matrix with a regularised diagonal is built by the caller as ordinary
+ * entries.  Every summation order is fixed by the matrix's own shape (a row's by its degree, a
+ * vector's by a constant slice length), no floating-point atomics: equal inputs give equal bits.
+ * CF_EINVAL: null argument, nsv == 0, nv < nsv, ortho_repeats outside 1..3, v0 all zero, CSRs that
+ * disagree; CF_ERANGE: nv > CF_SVD_MAX_NV.  rows == 0 or cols == 0 is a valid no-op. */
+#define CF_SVD_MAX_NV 256
+typedef struct cf_svd_stats {
+    uint32_t nconv;      /* converged triplets */
+    uint32_t passes;     /* restarts run (at most max_iter - 1) */
+    uint32_t products;   /* matrix-vector products, the residual checks' included */
+    float matvec_ms;     /* device time of the product kernels (HIP events) */
+    float ortho_ms;      /* of the orthogonalisation and normalisation kernels */
+    float rotate_ms;     /* of the Ritz rotation and restart-vector kernels */
+} cf_svd_stats;
+int cf_svd_fit(cf_ctx* ctx, uint32_t rows, uint32_t cols, const uint64_t* row_off, const uint32_t* row_col,
+               const float* row_val, const uint64_t* col_off, const uint32_t* col_row, const float* col_val,
+               uint32_t nsv, uint32_t nv, uint32_t max_iter, double tol, uint32_t ortho_repeats, const double* v0,
+               double* sigma, double* errest, double* err, double* U, double* V, uint32_t* kk_pass, double* first_ab,
+               cf_svd_stats* stats);
+/* The product kernel of cf_svd_fit on its own: y[n_out] = M x[n_in] for the CSR (off, nbr, val) with
+ * n_out rows (pass the column CSR for A^T x).  A row's summation order depends on its degree only. */
+int cf_svd_matvec(cf_ctx* ctx, uint32_t n_out, uint32_t n_in, const uint64_t* off, const uint32_t* nbr,
+                  const float* val, const double* x, double* y);
+/* The product kernel's cut between one wave per row and one workgroup per row; the other two cuts
+ * are cf_debug_als_low_max (several rows per wave up to it) and cf_debug_als_segment. */
+int cf_debug_svd_wave_max(void);
+/* The host SVD of cf_svd_fit's bidiagonal T on its own (csrc/cf_small_svd.hpp; needs no GPU):
+ * T is m x m row-major; a, PT (m x m row-major) and b (m, descending) with T = a diag(b) PT^T.
+ * Returns the number of sweeps, or CF_EINVAL. */
+int cf_debug_small_svd(int m, const double* T, double* a, double* b, double* PT);
 
 #ifdef __cplusplus
 }
