@@ -108,6 +108,7 @@ SIGNATURES = {
     "cf_graph_filter": (c_int, [c_void_p, c_int, c_uint32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_uint32, c_void_p]),
     "cf_graph_filter_timing": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cf_debug_filter_lanes": (c_int, [c_uint32, ctypes.c_uint64]),
     "cf_local_calc": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "cf_cost_split": (c_int, [c_uint32, c_void_p, c_int, c_void_p]),

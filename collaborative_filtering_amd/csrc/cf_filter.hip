@@ -131,7 +131,17 @@ void launch_step(int G, const FArgs& a, hipStream_t st) {
     }
 }
 
+// Lanes per vertex row, from the mean number of directed edges per vertex.
+int filter_lanes(uint32_t n_vertices, uint64_t nnz) {
+    const double mean_deg = n_vertices ? (double)nnz / n_vertices : 0.0;
+    return mean_deg >= 48.0 ? 64 : (mean_deg >= 8.0 ? 16 : 4);
+}
+
 }  // namespace
+
+extern "C" int cf_debug_filter_lanes(uint32_t n_vertices, uint64_t n_directed_edges) {
+    return filter_lanes(n_vertices, n_directed_edges);
+}
 
 extern "C" int cf_graph_filter(cf_ctx* ctx, int kind, uint32_t n_vertices, uint64_t n_lines, const uint32_t* va,
                                const uint32_t* vb, const double* w, const double* signal, const double* coeff,
@@ -169,8 +179,7 @@ extern "C" int cf_graph_filter(cf_ctx* ctx, int kind, uint32_t n_vertices, uint6
             wv[p] = w[l];
         }
     }
-    const double mean_deg = n_vertices ? (double)nnz / n_vertices : 0.0;
-    const int G = mean_deg >= 48.0 ? 64 : (mean_deg >= 8.0 ? 16 : 4);
+    const int G = filter_lanes(n_vertices, nnz);
     DevBuf d_row, d_col, d_w, d_wn, d_deg, d_x, d_v0, d_v1, d_v2, d_y;
     const size_t vb8 = sizeof(double) * std::max<uint32_t>(n_vertices, 1);
     CF_TRY(dev_alloc(ctx, d_row, sizeof(uint64_t) * (n_vertices + 1)));

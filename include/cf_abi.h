@@ -489,6 +489,9 @@ int cf_graph_filter(cf_ctx* ctx, int kind, uint32_t n_vertices, uint64_t n_lines
                     uint32_t n_coeff, double* out);
 /* Device time of the last cf_graph_filter's supersteps (HIP events) and its directed edges. */
 int cf_graph_filter_timing(cf_ctx* ctx, float* device_ms, uint64_t* n_edges);
+/* The lanes per vertex row (4, 16 or 64) that cf_graph_filter takes for a graph of n_vertices
+ * vertices and n_directed_edges kept directed edges (needs no GPU). */
+int cf_debug_filter_lanes(uint32_t n_vertices, uint64_t n_directed_edges);
 
 /* ---- ALS matrix factorization (als.cpp:290-371 on the synchronous engine) ----------------
  * R ~ U V^T over a bipartite graph: users 0..n_users-1 (the side with out-edges), items

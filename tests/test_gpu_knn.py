@@ -1,5 +1,15 @@
 """GPU parity of the kNN stage: knn2 (cf_item_cosine, int8 / fp32 MFMA) and knn3
-(cf_knn_predict) against the oracle's restatements of knn2.cpp / knn3.cpp."""
+(cf_knn_predict) against the oracle's restatements of knn2.cpp / knn3.cpp.
+
+knn3 at its branches: users with 255, 256, 257 and 600 test items (the block's row loop takes a
+second and a third trip), predictions of exactly x.5 (round half away from zero), the
+pred < 0.1 -> error 0 rule, the w > 0.1 edge at float32(0.1), and real ratings (the fp64 error
+sums and the integer / real switch of cf_knn_predict), each also against knn3_reference, a plain
+Python restatement with longdouble sums that makes no call into the oracle.
+Observed on the MI355X: integer-rating MSE and counts exact, predictions within 1e-12; the
+real-rating per-movie MSE deviates from the oracle's float accumulation by at most 4.9 x 2^-24
+relative at up to 49 test ratings per movie (bound cnt x 2^-24) and by 1.4 x 2^-24 from the
+exact mean."""
 import numpy as np
 import pytest
 
@@ -140,6 +150,195 @@ def test_knn3_matches_oracle(gpu_ctx):
     assert np.allclose(pred_g[order], pred_o, rtol=1e-12, atol=1e-12)
     assert np.array_equal(mse_g, mse_o)
     assert np.array_equal(cnt_g, np.diff(mo))
+
+
+# ---- knn3 at its branches -----------------------------------------------------------------------------
+def knn3_reference(W, off, items, rats):
+    """knn3.cpp:185-256 in plain Python, independent of the oracle: longdouble sums over the user's
+    other test items j with (double) w(m, j) > 0.1, pred = sum w r / sum w (0 without a neighbour),
+    tmp = 0 if pred < 0.1 else (float)(r - round(pred)) with round half away from zero
+    (math.floor(p + 0.5): p >= 0.1 there; numpy.round would go to even).  Returns (pred, tmp per
+    test rating as float32, per-movie test counts)."""
+    import math
+
+    W = np.asarray(W, np.float32)
+    off = np.asarray(off, np.int64)
+    rats = np.asarray(rats, np.float32)
+    pred = np.zeros(len(items))
+    tmp = np.zeros(len(items), np.float32)
+    for u in range(len(off) - 1):
+        b, e = int(off[u]), int(off[u + 1])
+        its = items[b:e].astype(np.int64)
+        r_u = rats[b:e].astype(np.longdouble)
+        for r in range(e - b):
+            w = W[its[r], its].astype(np.float64)
+            keep = w > 0.1
+            sw = w[keep].astype(np.longdouble).sum()
+            swr = (w[keep].astype(np.longdouble) * r_u[keep]).sum()
+            p = float(swr / sw) if keep.any() else 0.0
+            pred[b + r] = p
+            tmp[b + r] = np.float32(0.0) if p < 0.1 else np.float32(float(rats[b + r]) - math.floor(p + 0.5))
+    return pred, tmp, np.bincount(items.astype(np.int64), minlength=W.shape[0])
+
+
+def movie_mse_float(tmp, items, users, n_items):
+    """error_vertex_data (:249-253) by the reference's own formula: per movie, tmp * tmp accumulated
+    in float over its test ratings in user order, divided by the float count."""
+    mse = np.zeros(n_items, np.float32)
+    order = np.lexsort((users, items))
+    for m in range(n_items):
+        sel = order[items[order] == m]
+        if len(sel):
+            err = np.float32(0.0)
+            for t in tmp[sel]:
+                err = np.float32(err + np.float32(t * t))
+            mse[m] = np.float32(0.0) if np.isnan(err) else np.float32(err / np.float32(len(sel)))
+    return mse
+
+
+def knn3_oracle(W, off, items, rats):
+    """The oracle's knn3 on the same test ratings (it wants them per movie); pred back in user order."""
+    n_items = W.shape[0]
+    users = np.repeat(np.arange(len(off) - 1), np.diff(off.astype(np.int64)))
+    order = np.lexsort((users, items))
+    mo = np.zeros(n_items + 1, np.int64)
+    np.add.at(mo, items.astype(np.int64) + 1, 1)
+    mo = np.cumsum(mo)
+    pred_o, mse_o = orc.knn3(W, mo, users[order], np.asarray(rats, np.float32).astype(np.float64)[order])
+    pred = np.zeros(len(items))
+    pred[order] = pred_o
+    return pred, mse_o, users
+
+
+def users_with_sizes(ks, n_items, seed):
+    rng = np.random.default_rng(seed)
+    off = np.concatenate([[0], np.cumsum(ks)]).astype(np.uint64)
+    items = np.concatenate([np.sort(rng.choice(n_items, size=int(k), replace=False)) for k in ks]).astype(np.uint32)
+    return off, items
+
+
+def test_knn3_row_loop_takes_further_trips(gpu_ctx):
+    """One block per user, thread r taking test ratings r, r + 256, ...: users with 255, 256, 257 and
+    600 items (640 in all) beside small ones, against the oracle and against knn3_reference."""
+    rng = np.random.default_rng(21)
+    n_items = 640
+    W = np.where(rng.random((n_items, n_items)) < 0.3, rng.random((n_items, n_items)), 0.0).astype(np.float32)
+    np.fill_diagonal(W, 0.0)
+    gpu_ctx.upload_graph_dense(W)
+    ks = [3, 255, 1, 256, 17, 257, 39, 600, 2]
+    assert max(ks) > 2 * 256 and {255, 256, 257} <= set(ks)      # second and third trips, and the edge
+    off, items = users_with_sizes(ks, n_items, seed=22)
+    rats = rng.integers(1, 6, size=len(items)).astype(np.float32)
+    pred_g, mse_g, cnt_g = gpu_ctx.knn_predict(off, items, rats)
+    pred_o, mse_o, users = knn3_oracle(W, off, items, rats)
+    pred_r, tmp_r, cnt_r = knn3_reference(W, off, items, rats)
+    assert np.allclose(pred_g, pred_o, rtol=1e-12, atol=1e-12)
+    assert np.allclose(pred_g, pred_r, rtol=1e-12, atol=1e-12)
+    assert np.array_equal(mse_g, mse_o)
+    assert np.array_equal(mse_g, movie_mse_float(tmp_r, items, users, n_items))
+    assert np.array_equal(cnt_g, cnt_r) and int(cnt_g.sum()) == len(items) == sum(ks)
+    assert np.count_nonzero(pred_g[int(off[7]) + 512:int(off[8])]) > 50      # the third trip wrote predictions
+
+
+def test_knn3_ties_threshold_and_the_small_prediction_rule(gpu_ctx):
+    """Cases built exactly.  Equal weights 0.5 and integer ratings give predictions of exactly x.5,
+    which C's round and boost::math::round take away from zero (2.5 -> 3; numpy.round gives 2);
+    a user with one item has no neighbour (pred 0, error 0); ratings 0 and negative give
+    pred < 0.1 and error 0 (:243-244); float32(0.1) is an edge (its double value exceeds 0.1, :91)
+    and the next float32 below is not."""
+    n_items = 9
+    W = np.zeros((n_items, n_items), np.float32)
+    W[:3, :3] = 0.5
+    W[4, 5] = W[5, 4] = 0.5
+    below = np.nextafter(np.float32(0.1), np.float32(0))
+    assert float(np.float32(0.1)) > 0.1 > float(below)
+    W[6, 7], W[6, 8] = np.float32(0.1), below
+    W[7, 6] = W[8, 6] = 0.5
+    np.fill_diagonal(W, 0.0)
+    gpu_ctx.upload_graph_dense(W)
+    #        user A: ties      B          C: alone  D: pred < 0.1   E: the 0.1 edge
+    its = [[0, 1, 2],         [0, 1],    [3],      [4, 5],         [6, 7, 8]]
+    rts = [[2, 3, 4],         [1, 4],    [5],      [0, -2],        [5, 1, 3]]
+    want_pred = [3.5, 3.0, 2.5, 4.0, 1.0, 0.0, -2.0, 0.0, 1.0, 5.0, 5.0]
+    want_tmp = [2 - 4, 0, 4 - 3, 1 - 4, 4 - 1, 0, 0, 0, 5 - 1, 1 - 5, 3 - 5]
+    off = np.concatenate([[0], np.cumsum([len(i) for i in its])]).astype(np.uint64)
+    items = np.concatenate(its).astype(np.uint32)
+    rats = np.concatenate(rts).astype(np.float32)
+    pred_r, tmp_r, cnt_r = knn3_reference(W, off, items, rats)
+    assert np.array_equal(pred_r, want_pred) and np.array_equal(tmp_r, np.array(want_tmp, np.float32))
+    assert np.round(2.5) == 2.0      # the rounding this test tells apart
+    pred_g, mse_g, cnt_g = gpu_ctx.knn_predict(off, items, rats)
+    pred_o, mse_o, users = knn3_oracle(W, off, items, rats)
+    assert np.allclose(pred_g, pred_r, rtol=0, atol=1e-12) and np.allclose(pred_o, pred_r, rtol=0, atol=1e-12)
+    want_mse = np.array([(4 + 9) / 2, (0 + 9) / 2, 1, 0, 0, 0, 16, 16, 4], np.float32)
+    assert np.array_equal(movie_mse_float(tmp_r, items, users, n_items), want_mse)
+    assert np.array_equal(mse_g, want_mse) and np.array_equal(mse_o, want_mse)
+    assert np.array_equal(cnt_g, cnt_r) and list(cnt_g) == [2, 2, 1, 1, 1, 1, 1, 1, 1]
+
+
+def real_case(seed, n_items=80, n_users=150):
+    rng = np.random.default_rng(seed)
+    W = np.where(rng.random((n_items, n_items)) < 0.3, rng.random((n_items, n_items)), 0.0).astype(np.float32)
+    np.fill_diagonal(W, 0.0)
+    ks = list(rng.integers(1, 40, size=n_users)) + [n_items - 1]
+    off, items = users_with_sizes(ks, n_items, seed + 1)
+    return rng, W, off, items
+
+
+def check_real_path(gpu_ctx, W, off, items, rats, label):
+    """Predictions to 1e-12; per-movie MSE to cnt 2^-24 relative: the reference accumulates cnt
+    non-negative floats in float ((cnt - 1) roundings of 2^-24 each, nothing to cancel) where the
+    device sums the same floats in fp64 and rounds once.  Against the exact mean (longdouble) of
+    knn3_reference's errors this is a bound: the device makes two roundings (the sum, the
+    division; none at cnt = 1, where the sum is one float).  Against the oracle it is a first-order
+    figure: counting both divisions the strict worst case is (cnt + 2) 2^-24, which could exceed
+    cnt 2^-24 only if every rounding of both sides fell the same way."""
+    n_items = W.shape[0]
+    gpu_ctx.upload_graph_dense(W)
+    pred_g, mse_g, cnt_g = gpu_ctx.knn_predict(off, items, rats)
+    pred_o, mse_o, users = knn3_oracle(W, off, items, rats)
+    pred_r, tmp_r, cnt_r = knn3_reference(W, off, items, rats)
+    assert np.allclose(pred_g, pred_o, rtol=1e-12, atol=1e-12)
+    assert np.allclose(pred_g, pred_r, rtol=1e-12, atol=1e-12)
+    assert np.array_equal(cnt_g, cnt_r) and int(cnt_g.sum()) == len(items)
+    sq = (tmp_r * tmp_r).astype(np.longdouble)          # float products, as the kernel forms them
+    exact = np.zeros(n_items, np.longdouble)
+    np.add.at(exact, items.astype(np.int64), sq)
+    exact = exact / np.maximum(cnt_r, 1)
+    tol = cnt_r * 2.0 ** -24
+    dev_o = np.abs(mse_g.astype(np.float64) - mse_o.astype(np.float64))
+    dev_x = np.abs(mse_g.astype(np.longdouble) - exact)
+    rel = lambda d, ref: float(np.max(np.where(ref > 0, d / np.where(ref > 0, ref, 1), 0.0)))   # noqa: E731
+    print(f"{label}: knn3 real-rating MSE deviates by {rel(dev_o, mse_o) * 2 ** 24:.3g} x 2^-24 from the oracle, "
+          f"{rel(dev_x, exact) * 2 ** 24:.3g} x 2^-24 from the exact mean (largest count {int(cnt_r.max())})")
+    assert np.all(dev_o <= tol * mse_o)
+    assert np.all(dev_x <= tol * exact)
+    assert np.count_nonzero(mse_o) > n_items // 2
+    return mse_g, tmp_r, cnt_r
+
+
+def test_knn3_real_ratings(gpu_ctx):
+    """Two-decimal ratings take the fp64 sq_err_real sums (cf_knn_predict switches on integer_small)."""
+    rng, W, off, items = real_case(31)
+    rats = np.round(rng.uniform(0.5, 5.0, size=len(items)), 2).astype(np.float32)
+    assert np.any(rats != np.round(rats))
+    check_real_path(gpu_ctx, W, off, items, rats, "two-decimal ratings")
+
+
+def test_knn3_one_real_rating_switches_the_path(gpu_ctx):
+    """Integer ratings except one (3.25): the whole call takes the real path.  The integer path
+    truncates every squared error to an integer; on the movies where that changes the MSE by more
+    than the tolerance, agreement shows which path ran."""
+    rng, W, off, items = real_case(41)
+    rats = rng.integers(1, 6, size=len(items)).astype(np.float32)
+    odd = int(off[-2]) + 5                      # every other tmp is an integer: only this rating's movie can tell
+    rats[odd] = 3.25
+    mse_g, tmp_r, cnt_r = check_real_path(gpu_ctx, W, off, items, rats, "one real rating")
+    trunc = np.zeros(W.shape[0])
+    np.add.at(trunc, items.astype(np.int64), np.floor((tmp_r * tmp_r).astype(np.float64)))
+    trunc_mse = (trunc.astype(np.float32) / np.maximum(cnt_r, 1).astype(np.float32)).astype(np.float32)
+    told = np.abs(trunc_mse.astype(np.float64) - mse_g) > cnt_r * 2.0 ** -24 * mse_g
+    assert told[items[odd]], "the movie of the real rating tells the paths apart"
 
 
 def test_csr_graph_bit_identical_to_dense(gpu_ctx):
