@@ -18,6 +18,7 @@ CF_EINVAL = -1
 CF_ERANGE = -4
 CF_SVD_MAX_NV = 256
 CF_ALS_MAX_D = 64
+CF_TOPN_MAX_N = 1024
 CF_SIGS_OWN = 0
 CF_SIGS_COMPAT = 1
 CF_MAX_K = 192
@@ -146,6 +147,11 @@ SIGNATURES = {
     "cf_debug_small_svd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cf_debug_als_segment": (c_int, []),
     "cf_debug_als_low_max": (c_int, []),
+    "cf_mf_topn": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                           c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_set_topn_block": (c_int, [c_void_p, c_uint32]),
+    "cf_debug_topn_tile_users": (c_int, []),
+    "cf_debug_topn_tile_items": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }
@@ -204,6 +210,11 @@ class SvdStats(ctypes.Structure):
     """cf_svd_stats (cf_abi.h)."""
     _fields_ = [("nconv", c_uint32), ("passes", c_uint32), ("products", c_uint32), ("matvec_ms", c_float),
                 ("ortho_ms", c_float), ("rotate_ms", c_float)]
+
+
+class TopnStats(ctypes.Structure):
+    """cf_topn_stats (cf_abi.h)."""
+    _fields_ = [("blocks", c_uint32), ("n_nan", c_uint64), ("score_ms", c_float), ("select_ms", c_float)]
 
 
 EIGEN_SINK =ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))

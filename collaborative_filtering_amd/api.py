@@ -165,6 +165,19 @@ class SvdResult:
     rotate_ms: float
 
 
+@dataclass
+class TopnResult:
+    """Outcome of Context.mf_topn: per selected user j the count[j] best candidate items
+    items[j, :count[j]] with their scores, ordered by score descending and, among equal scores,
+    item ascending; the tail of a row is UINT32_MAX / 0.0.  stats is the cf_topn_stats of the
+    call (blocks, n_nan, score_ms, select_ms)."""
+
+    items: np.ndarray    # uint32[n_selected, N]
+    scores: np.ndarray   # float64[n_selected, N]
+    count: np.ndarray    # uint32[n_selected]
+    stats: "_native.TopnStats"
+
+
 def _csr(row, col, obs, n_rows):
     """Stable CSR of an edge list by row (edges of one row keep their input order)."""
     perm = np.argsort(row, kind="stable")
@@ -854,6 +867,49 @@ class Context:
                                             U.shape[1], ptr(U), ptr(V), ptr(Y), ptr(bu), ptr(bi), float(global_mean),
                                             float(minval), float(maxval), ptr(pred)), "cf_svdpp_predict")
         return pred
+
+    # -- top-N recommendation from fitted factors (no reference counterpart) ----------
+    def set_topn_block(self, users_per_block: int = 0):
+        """cf_set_topn_block: users per block of mf_topn (0 = from its fixed byte budget)."""
+        self._chk(self.lib.cf_set_topn_block(self.h, int(users_per_block)), "cf_set_topn_block")
+
+    def mf_topn(self, U, V, N, *, bias_user=None, bias_item=None, mean=0.0, exclude=None, users=None) -> "TopnResult":
+        """cf_mf_topn: for every user (or every user of `users`, in its order) the N best items by
+        U_u . V_i + (bias_item[i] + (mean + bias_user[u])), absent biases skipped, among the items
+        that are not in the user's exclusion list.  exclude: (user, item) index arrays of the pairs
+        to leave out (any order, repeats allowed).  A NaN score is never listed."""
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
+            raise ValueError("U and V must be n_users x D and n_items x D")
+        n_users, n_items, D, N = U.shape[0], V.shape[0], U.shape[1], int(N)
+        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
+        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
+        if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
+            raise ValueError("bias_user / bias_item do not hold one value per user / item")
+        eoff = eitem = None
+        if exclude is not None:
+            eu = np.ascontiguousarray(exclude[0], dtype=np.uint32)
+            ei = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+            if len(eu) != len(ei):
+                raise ValueError("exclude holds different numbers of users and items")
+            if len(eu) and int(eu.max()) >= n_users:
+                raise ValueError("excluded user index out of range")
+            eoff, eitem, _ = _csr(eu, ei, np.zeros(len(eu), np.float32), n_users)
+            if not len(eitem):
+                eitem = np.zeros(1, np.uint32)   # a valid pointer for an empty list
+        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
+        n_out = n_users if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.uint32)
+        items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
+        count = np.zeros(n_out, dtype=np.uint32)
+        st = _native.TopnStats()
+        self._chk(self.lib.cf_mf_topn(self.h, n_users, n_items, D, ptr(U), ptr(V), ptr(bu), ptr(bi), float(mean),
+                                      ptr(eoff), ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(items),
+                                      ptr(scores), ptr(count), byref(st)), "cf_mf_topn")
+        return TopnResult(items, scores, count, st)
 
     # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
     @staticmethod

@@ -178,6 +178,8 @@ struct cf_ctx {
     // SVD++ (cf_svdpp_timing): the same of the last cf_svdpp_fit per kernel kind: phase-1 user
     // reduction, phase-2 user reduction, item message reduction
     float svdpp_reduce_ms[3] = {0.0f, 0.0f, 0.0f};
+    // top-N (cf_topn.hip): users per block forced by cf_set_topn_block (0 = from the byte budget)
+    uint32_t topn_block = 0;
 };
 
 // One launch of the eigen / predict kernels covers the users of one k-bucket.

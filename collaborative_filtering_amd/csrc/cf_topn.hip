@@ -1,0 +1,519 @@
+// cf_topn.hip -- top-N recommendation from fitted factors (cf_mf_topn): for every selected user
+// the N best items by score = U_u . V_i (+ biases) among the items the user has not rated.
+// The reference stops at the factor files and the PREDICT edges (als.cpp:493-510); this is the
+// scorer the five factorizers (als, sgd, biassgd, svdpp, svd) lacked.  DESIGN 3.16.
+//
+// The selected users run in blocks of `ub` users whose scores live in a panel of 64-bit keys,
+// key[user in block][item] (row stride n_items, carved from the context's ALS workspace):
+//   topn_score_kernel    one workgroup per (kTU users x kTI items) tile: both tiles' rows staged in
+//                        LDS kKC deep (zero-padded), 16 x 16 fp64 MFMA accumulators, and an
+//                        epilogue that adds the bias term and stores the order-preserving key
+//   topn_exclude_kernel  one thread per exclusion edge of the block's users: key = kKeyExcluded
+//                        (a plain store: repeats and order do not matter)
+//   topn_select_kernel   one workgroup per user row: 8 x 8-bit radix select of the K-th largest
+//                        key, K = min(N, candidates), compaction of the keys above it and of the
+//                        lowest-index ties at it, a bitonic sort of the <= 1024 survivors in LDS by
+//                        (key descending, item ascending), and the keys mapped back to doubles
+// Keys: the double's bits with the sign bit set for positives and every bit flipped for
+// negatives, -0 taken as +0.  Keys 0 and 1 are images of NaN bit patterns only, so they are free:
+// 0 marks an excluded item, 1 a NaN score; both rank below every real score and are never listed.
+// A score is one MFMA chain over its own two rows, so its bits do not depend on the tile it
+// falls in, the block size or the other users; the only atomics are integer counts (the LDS
+// histogram, the NaN count).
+
+// of cf_mf_common.h this file takes the workspace helpers and the block scan, not its kernels
+#pragma clang diagnostic ignored "-Wunused-function"
+#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
+#include "cf_mf_common.h"
+
+namespace {
+
+using d4 = __attribute__((ext_vector_type(4))) double;
+
+constexpr int kTU = 64;                  // users per score tile
+constexpr int kTI = 64;                  // items per score tile
+constexpr int kKC = 32;                  // depth staged per pass (Dp <= 64: at most two passes)
+constexpr int kSt = kKC + 2;             // LDS row stride in doubles: 2 mod 4, so the 32 lanes of a
+                                         // half wave (16 rows x 2 depths) read 32 distinct 8-byte banks
+constexpr int kMaxN = CF_TOPN_MAX_N;
+constexpr uint64_t kKeyExcluded = 0ull;
+constexpr uint64_t kKeyNaN = 1ull;
+constexpr uint64_t kSign = 0x8000000000000000ull;
+constexpr size_t kPanelBudget = (size_t)1 << 30;   // bytes of keys per user block (fixed, never from free HBM)
+
+static_assert(kAT == 256 && kWaves == 4, "the score tile is four waves of 32 x 32");
+
+__device__ __forceinline__ uint64_t score_key(double s) {
+    if (s != s) return kKeyNaN;
+    if (s == 0.0) s = 0.0;   // -0 ranks (and reads back) as +0
+    const uint64_t b = (uint64_t)__double_as_longlong(s);
+    return (b & kSign) ? ~b : (b | kSign);
+}
+
+__device__ __forceinline__ double key_score(uint64_t k) {
+    return __longlong_as_double((long long)((k & kSign) ? (k ^ kSign) : ~k));
+}
+
+// Tile (ut, it) of the block: rows r0 .. r0 + kTU of the block's nb users (user of row r:
+// sel[b0 + r], or b0 + r without a selection), items i0 .. i0 + kTI.  Wave w owns the 32 x 32
+// quadrant (w >> 1, w & 1) as 2 x 2 MFMA tiles: A lane l = U row (l & 15), depth (l >> 4); B lane
+// l = V row (l & 15), depth (l >> 4); result q of lane l = user (l >> 4) + 4 q, item l & 15.
+__global__ __launch_bounds__(kAT) void topn_score_kernel(const double* __restrict__ U, const double* __restrict__ V,
+                                                        int D, uint32_t n_items, uint32_t n_it,
+                                                        const uint32_t* __restrict__ sel, uint32_t b0, uint32_t nb,
+                                                        const double* __restrict__ bu, const double* __restrict__ bi,
+                                                        double mean, uint64_t* __restrict__ panel) {
+    __shared__ double s_u[kTU * kSt];
+    __shared__ double s_v[kTI * kSt];
+    const uint32_t ut = blockIdx.x / n_it, it = blockIdx.x % n_it;
+    const uint32_t r0 = ut * kTU, i0 = it * kTI;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wu = (wave >> 1) * 32, wi = (wave & 1) * 32;
+    const int Dp = (D + 3) & ~3;
+    d4 acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int d0 = 0; d0 < Dp; d0 += kKC) {
+        const int dc = min(kKC, Dp - d0);   // a multiple of 4
+        if (d0) __syncthreads();
+        for (int idx = threadIdx.x; idx < kTU * dc; idx += kAT) {
+            const int r = idx / dc, dd = idx - r * dc, d = d0 + dd;
+            double a = 0.0, b = 0.0;
+            if (d < D) {
+                if (r0 + r < nb) {
+                    const uint32_t u = sel ? sel[b0 + r0 + r] : b0 + r0 + r;
+                    a = U[(size_t)u * D + d];
+                }
+                if ((uint64_t)i0 + r < n_items) b = V[((size_t)i0 + r) * D + d];
+            }
+            s_u[r * kSt + dd] = a;
+            s_v[r * kSt + dd] = b;
+        }
+        __syncthreads();
+        for (int kk = 0; kk < dc; kk += 4) {
+            double av[2], bv[2];
+#pragma unroll
+            for (int x = 0; x < 2; ++x) av[x] = s_u[(wu + x * 16 + (lane & 15)) * kSt + kk + (lane >> 4)];
+#pragma unroll
+            for (int y = 0; y < 2; ++y) bv[y] = s_v[(wi + y * 16 + (lane & 15)) * kSt + kk + (lane >> 4)];
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y)
+                    acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
+        }
+    }
+    const bool biased = bu || bi;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t r = r0 + wu + x * 16 + (lane >> 4) + 4 * q;
+            if (r >= nb) continue;
+            double tu = mean;   // mean + bias_user[u]
+            if (bu) tu = mean + bu[sel ? sel[b0 + r] : b0 + r];
+            uint64_t* prow = panel + (size_t)r * n_items;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                const uint64_t i = (uint64_t)i0 + wi + y * 16 + (lane & 15);
+                if (i >= n_items) continue;
+                double s = acc[x][y][q];
+                if (biased) s = s + (bi ? bi[i] + tu : tu);
+                prow[i] = score_key(s);
+            }
+        }
+}
+
+// Edge e of the block: the (e - first edge of its row)-th exclusion of the row r whose range in
+// sel_off (the prefix of the selected users' exclusion counts; excl_off itself without a
+// selection) holds sel_off[b0] + e.
+__global__ __launch_bounds__(kAT) void topn_exclude_kernel(const uint64_t* __restrict__ excl_off,
+                                                          const uint32_t* __restrict__ excl_item,
+                                                          const uint64_t* __restrict__ sel_off,
+                                                          const uint32_t* __restrict__ sel, uint32_t b0, uint32_t nb,
+                                                          uint32_t n_items, uint64_t n_edges,
+                                                          uint64_t* __restrict__ panel) {
+    const uint64_t e = (uint64_t)blockIdx.x * kAT + threadIdx.x;
+    if (e >= n_edges) return;
+    const uint64_t target = sel_off[b0] + e;
+    uint32_t lo = 0, hi = nb;   // first row whose range starts above target
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (sel_off[b0 + mid] <= target) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return;
+    const uint32_t r = lo - 1;
+    const uint32_t u = sel ? sel[b0 + r] : b0 + r;
+    const uint32_t item = excl_item[excl_off[u] + (target - sel_off[b0 + r])];
+    if (item < n_items) panel[(size_t)r * n_items + item] = kKeyExcluded;
+}
+
+// One histogram increment per active lane, called by whole waves.  The keys of a row share their
+// high bytes, so in the first passes most lanes of a wave hit one bin, and 64 LDS atomics on one
+// address run one after the other: up to kAggRounds times the lanes that share the first active
+// lane's bin add their count once; what is left (spread bins) adds lane by lane.  Integer sums:
+// the order does not show.
+constexpr int kAggRounds = 4;
+__device__ __forceinline__ void hist_add(unsigned int* s_hist, bool active, unsigned int bin, int lane) {
+#pragma unroll
+    for (int round = 0; round < kAggRounds; ++round) {
+        const unsigned long long act = __ballot(active);
+        if (!act) return;   // the whole wave
+        const int first = __ffsll((long long)act) - 1;
+        const unsigned int b = (unsigned int)__shfl((int)bin, first);
+        const bool mine = active && bin == b;
+        const unsigned long long same = __ballot(mine);
+        if (lane == first) atomicAdd(&s_hist[b], (unsigned int)__popcll(same));
+        if (mine) active = false;
+    }
+    if (active) atomicAdd(&s_hist[bin], 1u);
+}
+
+// Keys first, first + STRIDE, .. (kUnroll of them) of a row of n keys, requested together: a walk
+// with one load in flight per lane is bound by the load latency, not by L2 or HBM.  Past the end
+// of the row: kKeyExcluded, which no pass counts.
+constexpr int kUnroll = 8;
+template <int STRIDE>
+__device__ __forceinline__ void load_keys(const uint64_t* __restrict__ row, uint64_t first, uint64_t n,
+                                          uint64_t (&kv)[kUnroll]) {
+#pragma unroll
+    for (int j = 0; j < kUnroll; ++j) {
+        const uint64_t i = first + (uint64_t)j * STRIDE;
+        kv[j] = i < n ? row[i] : kKeyExcluded;
+    }
+}
+
+__device__ __forceinline__ bool topn_before(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
+    return ka > kb || (ka == kb && ia < ib);
+}
+
+__global__ __launch_bounds__(kAT) void topn_select_kernel(const uint64_t* __restrict__ panel, uint32_t n_items,
+                                                         uint32_t N, uint32_t* __restrict__ out_items,
+                                                         double* __restrict__ out_scores,
+                                                         uint32_t* __restrict__ out_count,
+                                                         unsigned long long* __restrict__ n_nan) {
+    __shared__ unsigned int s_hist[256];
+    __shared__ unsigned int s_sel[2];
+    __shared__ uint32_t s_scan[kWaves + 1];
+    __shared__ unsigned int s_cnt[2][kWaves];
+    __shared__ uint64_t s_key[kMaxN];
+    __shared__ uint32_t s_item[kMaxN];
+    const uint64_t* row = panel + (size_t)blockIdx.x * n_items;
+    uint32_t* o_items = out_items + (size_t)blockIdx.x * N;
+    double* o_scores = out_scores + (size_t)blockIdx.x * N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+    // candidates (keys above the two markers) and NaN scores of the row
+    unsigned int cv = 0, cn = 0;
+    uint64_t kv[kUnroll];
+    for (uint64_t i0 = 0; i0 < n_items; i0 += (uint64_t)kAT * kUnroll) {
+        load_keys<kAT>(row, i0 + threadIdx.x, n_items, kv);
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) {
+            cv += kv[j] > kKeyNaN;
+            cn += kv[j] == kKeyNaN;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        cv += __shfl_xor(cv, o);
+        cn += __shfl_xor(cn, o);
+    }
+    if (lane == 0) {
+        s_cnt[0][wave] = cv;
+        s_cnt[1][wave] = cn;
+    }
+    __syncthreads();
+    unsigned int valid = 0, nans = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        valid += s_cnt[0][w];
+        nans += s_cnt[1][w];
+    }
+    if (threadIdx.x == 0 && nans) atomicAdd(n_nan, (unsigned long long)nans);
+    const uint32_t K = min(N, valid);
+    if (threadIdx.x == 0) out_count[blockIdx.x] = K;
+    for (uint32_t p = K + threadIdx.x; p < N; p += kAT) {
+        o_items[p] = 0xffffffffu;
+        o_scores[p] = 0.0;
+    }
+    if (K == 0) return;   // the whole workgroup
+
+    // the K-th largest key T, and rem = how many of the keys equal to T are listed
+    uint64_t prefix = 0, mask = 0;
+    uint32_t rem = K;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        __syncthreads();
+        s_hist[threadIdx.x] = 0u;   // kAT == 256 bins
+        __syncthreads();
+        for (uint64_t i0 = 0; i0 < n_items; i0 += (uint64_t)kAT * kUnroll) {   // whole waves enter hist_add
+            load_keys<kAT>(row, i0 + threadIdx.x, n_items, kv);
+#pragma unroll
+            for (int j = 0; j < kUnroll; ++j)
+                hist_add(s_hist, kv[j] > kKeyNaN && (kv[j] & mask) == prefix, (unsigned int)(kv[j] >> shift) & 255u, lane);
+        }
+        __syncthreads();
+        // thread t looks at bin 255 - t: `above` = the keys in higher bins; the bin that holds the
+        // rem-th largest is the one with above < rem <= above + its count (bin 0 catches the rest)
+        const unsigned int mine = s_hist[255 - threadIdx.x];
+        unsigned int all;
+        const unsigned int above = block_excl_scan(mine, s_scan, &all);
+        if (above < rem && (rem <= above + mine || threadIdx.x == kAT - 1)) {
+            s_sel[0] = 255u - threadIdx.x;
+            s_sel[1] = above;
+        }
+        __syncthreads();
+        prefix |= (uint64_t)s_sel[0] << shift;
+        mask |= 255ull << shift;
+        rem -= s_sel[1];
+    }
+    const uint64_t T = prefix;
+    const uint32_t G = K - rem;   // keys above T
+
+    // compaction: wave w walks its contiguous quarter of the row, 64 items at a time, so the ties
+    // are numbered in item order; keys above T fill slots [0, G), the first rem ties [G, K)
+    const uint64_t per = ((((uint64_t)n_items + kWaves - 1) / kWaves) + 63) & ~63ull;
+    const uint64_t beg = min((uint64_t)n_items, per * wave), end = min((uint64_t)n_items, beg + per);
+    unsigned int cg = 0, ct = 0;
+    for (uint64_t i0 = beg; i0 < end; i0 += 64 * kUnroll) {
+        load_keys<64>(row, i0 + lane, end, kv);
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) {
+            cg += kv[j] > T;
+            ct += kv[j] == T;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        cg += __shfl_xor(cg, o);
+        ct += __shfl_xor(ct, o);
+    }
+    __syncthreads();   // s_cnt was read above
+    if (lane == 0) {
+        s_cnt[0][wave] = cg;
+        s_cnt[1][wave] = ct;
+    }
+    __syncthreads();
+    unsigned int gpos = 0, tpos = 0;
+    for (int w = 0; w < wave; ++w) {
+        gpos += s_cnt[0][w];
+        tpos += s_cnt[1][w];
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (uint64_t i0 = beg; i0 < end; i0 += 64 * kUnroll) {
+        load_keys<64>(row, i0 + lane, end, kv);
+#pragma unroll
+        for (int j = 0; j < kUnroll; ++j) {   // in item order
+            const uint64_t i = i0 + (uint64_t)j * 64 + lane;
+            const bool gt = kv[j] > T, tie = kv[j] == T;   // T is a real key: the fill value is neither
+            const unsigned long long bg = __ballot(gt), bt = __ballot(tie);
+            if (gt) {
+                const unsigned int p = gpos + (unsigned int)__popcll(bg & below);
+                if (p < G) {
+                    s_key[p] = kv[j];
+                    s_item[p] = (uint32_t)i;
+                }
+            }
+            if (tie) {
+                const unsigned int tr = tpos + (unsigned int)__popcll(bt & below);
+                if (tr < rem) {
+                    s_key[G + tr] = kv[j];
+                    s_item[G + tr] = (uint32_t)i;
+                }
+            }
+            gpos += (unsigned int)__popcll(bg);
+            tpos += (unsigned int)__popcll(bt);
+        }
+    }
+    uint32_t P = 1;
+    while (P < K) P <<= 1;   // <= kMaxN
+    for (uint32_t p = K + threadIdx.x; p < P; p += kAT) {
+        s_key[p] = kKeyExcluded;
+        s_item[p] = 0xffffffffu;
+    }
+    __syncthreads();
+
+    // bitonic sort of the P slots by (key descending, item ascending); the padding sorts last
+    for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < P; i += kAT) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint64_t ka = s_key[i], kb = s_key[l];
+                    const uint32_t ia = s_item[i], ib = s_item[l];
+                    const bool swap = (i & k) == 0 ? topn_before(kb, ib, ka, ia) : topn_before(ka, ia, kb, ib);
+                    if (swap) {
+                        s_key[i] = kb;
+                        s_item[i] = ib;
+                        s_key[l] = ka;
+                        s_item[l] = ia;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    for (uint32_t p = threadIdx.x; p < K; p += kAT) {
+        o_items[p] = s_item[p];
+        o_scores[p] = key_score(s_key[p]);
+    }
+}
+
+struct TopnLayout {
+    double* U;
+    double* V;
+    double* bu;
+    double* bi;
+    uint64_t* excl_off;
+    uint32_t* excl_item;
+    uint64_t* sel_off;
+    uint32_t* sel;
+    uint64_t* panel;
+    uint32_t* out_items;
+    double* out_scores;
+    uint32_t* out_count;
+    unsigned long long* n_nan;
+};
+
+// Users per block: the forced value, or as many rows of n_items keys as fit the budget (whole
+// score tiles when at least one fits); at least 1, at most the selection.
+uint32_t topn_block_users(const cf_ctx* ctx, uint32_t n_items, uint32_t n_out) {
+    uint64_t ub = ctx->topn_block;
+    if (!ub) {
+        ub = std::max<uint64_t>(1, kPanelBudget / ((uint64_t)n_items * sizeof(uint64_t)));
+        if (ub >= (uint64_t)kTU) ub -= ub % kTU;
+    }
+    return (uint32_t)std::min<uint64_t>(ub, n_out);
+}
+
+}  // namespace
+
+extern "C" int cf_debug_topn_tile_users(void) { return kTU; }
+extern "C" int cf_debug_topn_tile_items(void) { return kTI; }
+
+extern "C" int cf_set_topn_block(cf_ctx* ctx, uint32_t users_per_block) {
+    if (!ctx) return CF_EINVAL;
+    ctx->topn_block = users_per_block;
+    return CF_OK;
+}
+
+extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
+                          const double* bias_user, const double* bias_item, double mean, const uint64_t* excl_off,
+                          const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user, uint32_t N,
+                          uint32_t* items, double* scores, uint32_t* count, cf_topn_stats* stats) {
+    if (!ctx) return CF_EINVAL;
+    const std::string fn = "cf_mf_topn";
+    if (D == 0) return cf_set_error(ctx, CF_ERANGE, fn + ": D = 0");
+    if (D > CF_ALS_MAX_D) return cf_set_error(ctx, CF_ERANGE, fn + ": D above CF_ALS_MAX_D");
+    if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
+    if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
+    if ((excl_off == nullptr) != (excl_item == nullptr))
+        return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
+    const uint32_t n_out = sel_user ? n_sel : n_users;
+    if (sel_user)
+        for (uint32_t j = 0; j < n_sel; ++j)
+            if (sel_user[j] >= n_users) return cf_set_error(ctx, CF_EINVAL, fn + ": selected user out of range");
+    if (n_out && !count) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    if (excl_off && n_users) CF_TRY(check_csr(ctx, "cf_mf_topn", "exclusion", n_users, excl_off, excl_item, n_items));
+    if (stats) *stats = cf_topn_stats{};
+    for (uint32_t j = 0; j < n_out; ++j) count[j] = 0;
+    if (n_out == 0 || n_items == 0) return CF_OK;
+    if (!U || !V || !items || !scores) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    CF_TRY(set_device(ctx));
+
+    const uint64_t nnz = excl_off ? excl_off[n_users] : 0;
+    // the selection's own prefix of exclusion counts; without a selection it is excl_off
+    std::vector<uint64_t> sel_off;
+    if (sel_user && nnz) {
+        sel_off.assign((size_t)n_sel + 1, 0);
+        for (uint32_t j = 0; j < n_sel; ++j)
+            sel_off[j + 1] = sel_off[j] + (excl_off[sel_user[j] + 1] - excl_off[sel_user[j]]);
+    }
+    const uint32_t ub = topn_block_users(ctx, n_items, n_out);
+    const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
+    if ((uint64_t)((ub + kTU - 1) / kTU) * n_it > 0x7fffffffull)
+        return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
+
+    TopnLayout L{};
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver c;
+        if (pass) c.base = static_cast<char*>(ctx->d_als);
+        L.U = c.take<double>((size_t)n_users * D);
+        L.V = c.take<double>((size_t)n_items * D);
+        L.bu = bias_user ? c.take<double>(n_users) : nullptr;
+        L.bi = bias_item ? c.take<double>(n_items) : nullptr;
+        L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
+        L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
+        L.sel_off = !sel_off.empty() ? c.take<uint64_t>(sel_off.size()) : nullptr;
+        L.sel = sel_user ? c.take<uint32_t>(n_sel) : nullptr;
+        L.panel = c.take<uint64_t>((size_t)ub * n_items);
+        L.out_items = c.take<uint32_t>((size_t)ub * N);
+        L.out_scores = c.take<double>((size_t)ub * N);
+        L.out_count = c.take<uint32_t>(ub);
+        L.n_nan = c.take<unsigned long long>(1);
+        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
+    }
+    CF_HIP_CHECK(ctx, hipMemcpy(L.U, U, sizeof(double) * (size_t)n_users * D, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(L.V, V, sizeof(double) * (size_t)n_items * D, hipMemcpyHostToDevice));
+    if (bias_user) CF_HIP_CHECK(ctx, hipMemcpy(L.bu, bias_user, sizeof(double) * n_users, hipMemcpyHostToDevice));
+    if (bias_item) CF_HIP_CHECK(ctx, hipMemcpy(L.bi, bias_item, sizeof(double) * n_items, hipMemcpyHostToDevice));
+    if (nnz) {
+        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
+        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+    }
+    if (L.sel_off)
+        CF_HIP_CHECK(ctx, hipMemcpy(L.sel_off, sel_off.data(), sizeof(uint64_t) * sel_off.size(), hipMemcpyHostToDevice));
+    if (sel_user) CF_HIP_CHECK(ctx, hipMemcpy(L.sel, sel_user, sizeof(uint32_t) * n_sel, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemset(L.n_nan, 0, sizeof(unsigned long long)));
+
+    MfEvents<3> evs;
+    for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
+    hipStream_t st = nullptr;
+    const uint64_t* d_sel_off = L.sel_off ? L.sel_off : L.excl_off;
+    const uint64_t* h_sel_off = !sel_off.empty() ? sel_off.data() : excl_off;
+    const double bias_mean = (bias_user || bias_item) ? mean : 0.0;
+    uint32_t blocks = 0;
+    float score_ms = 0.0f, select_ms = 0.0f;
+    for (uint32_t b0 = 0; b0 < n_out; b0 += ub) {
+        const uint32_t nb = std::min(ub, n_out - b0);
+        const uint32_t tiles = ((nb + kTU - 1) / kTU) * n_it;
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
+        hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)L.U, (const double*)L.V,
+                           (int)D, n_items, n_it, (const uint32_t*)L.sel, b0, nb, (const double*)L.bu,
+                           (const double*)L.bi, bias_mean, L.panel);
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
+        const uint64_t edges = nnz ? h_sel_off[b0 + nb] - h_sel_off[b0] : 0;
+        if (edges) {
+            if ((edges + kAT - 1) / kAT > 0x7fffffffull)
+                return cf_set_error(ctx, CF_ERANGE, fn + ": exclusions of one user block exceed the launch grid");
+            hipLaunchKernelGGL(topn_exclude_kernel, dim3((unsigned)((edges + kAT - 1) / kAT)), dim3(kAT), 0, st,
+                               (const uint64_t*)L.excl_off, (const uint32_t*)L.excl_item, d_sel_off,
+                               (const uint32_t*)L.sel, b0, nb, n_items, edges, L.panel);
+        }
+        hipLaunchKernelGGL(topn_select_kernel, dim3(nb), dim3(kAT), 0, st, (const uint64_t*)L.panel, n_items, N,
+                           L.out_items, L.out_scores, L.out_count, L.n_nan);
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
+        CF_HIP_CHECK(ctx, hipGetLastError());
+        // the copies wait for the stream
+        CF_HIP_CHECK(ctx, hipMemcpy(items + (size_t)b0 * N, L.out_items, sizeof(uint32_t) * (size_t)nb * N, hipMemcpyDeviceToHost));
+        CF_HIP_CHECK(ctx, hipMemcpy(scores + (size_t)b0 * N, L.out_scores, sizeof(double) * (size_t)nb * N, hipMemcpyDeviceToHost));
+        CF_HIP_CHECK(ctx, hipMemcpy(count + b0, L.out_count, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+        float a = 0.0f, b = 0.0f;
+        (void)hipEventElapsedTime(&a, evs.e[0], evs.e[1]);
+        (void)hipEventElapsedTime(&b, evs.e[1], evs.e[2]);
+        score_ms += a;
+        select_ms += b;
+        ++blocks;
+    }
+    unsigned long long n_nan = 0;
+    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan, L.n_nan, sizeof(n_nan), hipMemcpyDeviceToHost));
+    if (stats) {
+        stats->blocks = blocks;
+        stats->n_nan = n_nan;
+        stats->score_ms = score_ms;
+        stats->select_ms = select_ms;
+    }
+    return CF_OK;
+}

@@ -1,0 +1,122 @@
+// recommend -- the N best unrated items of every user from the factor files of als, sgd, biassgd,
+// svdpp or svd (--predictions P there).  No reference counterpart: its programs save the PREDICT
+// edges only (als.cpp:493-510), so scoring every item of every user meant listing every pair.
+//   recommend --factors P [--matrix DIR] --topn N [--bias] [--mean M] --output R [--nshards 4] [--users FILE]
+//   P.U_* / P.V_*        factor lines "id f0 f1 .. " or "id) f0 f1 .. " (cf_factor_io.hpp); D is the
+//                        first line's width; --bias also reads P.bias.U_* / P.bias.V_* and adds
+//                        bias_item + (M + bias_user) to every score (biassgd.cpp:400-403)
+//   --matrix DIR         every TRAIN and VALIDATE edge of DIR is excluded (.predict pairs stay
+//                        candidates); a user or item of DIR without a factor line is fatal
+//   --users FILE         one user id per line: only their lists, in that order (default: every
+//                        user of P.U_*, ascending id)
+//   R_<i>_of_<nshards>   "user\titem\tscore" per listed item in rank order per user, score as %g,
+//                        sharded by user id like the predictions (cf_mf_cli.hpp write_predictions)
+#include <cstdio>
+#include <cstring>
+
+#include "cf_factor_io.hpp"
+#include "cf_mf_cli.hpp"
+
+int main(int argc, char** argv) {
+    const std::string factors = cfcli::opt(argc, argv, "factors", "");
+    const std::string matrix = cfcli::opt(argc, argv, "matrix", "");
+    const std::string output = cfcli::opt(argc, argv, "output", "");
+    const std::string topn = cfcli::opt(argc, argv, "topn", "");
+    const std::string users_file = cfcli::opt(argc, argv, "users", "");
+    const double mean = std::stod(cfcli::opt(argc, argv, "mean", "0"));
+    const int nshards = std::stoi(cfcli::opt(argc, argv, "nshards", "4"));
+    bool bias = false;
+    for (int i = 1; i < argc; ++i) bias = bias || std::strcmp(argv[i], "--bias") == 0;
+    if (factors.empty() || output.empty() || topn.empty())
+        cfcli::die("usage: recommend --factors P [--matrix DIR] --topn N [--bias] [--mean M] --output R [--nshards 4] [--users FILE]");
+    const uint32_t N = (uint32_t)std::stoul(topn);
+    if (N == 0 || N > CF_TOPN_MAX_N) cfcli::die("--topn must be between 1 and " + std::to_string(CF_TOPN_MAX_N));
+    if (nshards < 1) cfcli::die("--nshards must be at least 1");
+
+    const cfmf::Factors fu = cfmf::read_factors(factors + ".U");
+    const cfmf::Factors fv = cfmf::read_factors(factors + ".V");
+    if (fu.width != fv.width)
+        cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) + " values per line, " +
+                   factors + ".V " + std::to_string(fv.width));
+    const uint32_t D = fu.width, nu = fu.ids.size(), nm = fv.ids.size();
+    if (D > CF_ALS_MAX_D) cfcli::die("D = " + std::to_string(D) + " is above " + std::to_string(CF_ALS_MAX_D));
+    std::vector<double> bu, bi;
+    if (bias) {
+        bu = cfmf::read_bias(factors + ".bias.U", fu);
+        bi = cfmf::read_bias(factors + ".bias.V", fv);
+    }
+
+    // exclusions: the TRAIN and VALIDATE edges, as a CSR by user
+    cfmf::Csr excl;
+    if (!matrix.empty()) {
+        std::vector<uint32_t> eu, em;
+        for (const cfio::RoleRating& r : cfio::load_movielens_roles(matrix)) {
+            const auto u = fu.ids.at.find(r.user);
+            if (u == fu.ids.at.end())
+                cfcli::die("user " + std::to_string(r.user) + " of " + matrix + " has no line in " + factors + ".U_*");
+            const auto m = fv.ids.at.find(r.item);
+            if (m == fv.ids.at.end())
+                cfcli::die("item " + std::to_string(r.item) + " of " + matrix + " has no line in " + factors + ".V_*");
+            if (r.role == cfio::kPredict) continue;
+            eu.push_back(u->second);
+            em.push_back(m->second);
+        }
+        excl = cfmf::build_csr(nu, eu, em, std::vector<float>(eu.size(), 0.0f));
+        if (excl.nbr.empty()) excl.nbr.push_back(0);   // a valid pointer for an empty list
+    }
+
+    std::vector<uint32_t> sel;
+    if (!users_file.empty()) {
+        const std::string text = cfio::read_file(users_file);
+        const char* p = text.data();
+        const char* e = p + text.size();
+        while (p < e) {
+            if (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') {
+                ++p;
+                continue;
+            }
+            uint32_t id = 0;
+            const auto r = std::from_chars(p, e, id);
+            if (r.ec != std::errc()) cfcli::die("--users: " + users_file + " holds something that is not a user id");
+            p = r.ptr;
+            const auto u = fu.ids.at.find(id);
+            if (u == fu.ids.at.end()) cfcli::die("user " + std::to_string(id) + " of " + users_file + " has no line in " + factors + ".U_*");
+            sel.push_back(u->second);
+        }
+    }
+    const bool selected = !users_file.empty();
+    const uint32_t n_out = selected ? (uint32_t)sel.size() : nu;
+    if (selected && sel.empty()) sel.push_back(0);
+
+    std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
+    std::vector<uint32_t> items((size_t)n_out * N), count(n_out);
+    std::vector<double> scores((size_t)n_out * N);
+    cf_ctx* ctx = cfcli::open_device();
+    cf_topn_stats st{};
+    cfcli::check(ctx,
+                 cf_mf_topn(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr, bias ? bi.data() : nullptr,
+                            mean, matrix.empty() ? nullptr : excl.off.data(), matrix.empty() ? nullptr : excl.nbr.data(),
+                            selected ? n_out : 0, selected ? sel.data() : nullptr, N, items.data(), scores.data(),
+                            count.data(), &st),
+                 "cf_mf_topn");
+    std::printf("User blocks: %u  scoring kernels: %.3f ms  exclusion and selection kernels: %.3f ms\n", st.blocks,
+                st.score_ms, st.select_ms);
+    if (st.n_nan) std::printf("warning: %llu scores were NaN and are not listed\n", (unsigned long long)st.n_nan);
+
+    cfio::ShardWriter w(".", output, nshards);
+    for (uint32_t j = 0; j < n_out; ++j) {
+        const uint32_t uid = fu.ids.ids[selected ? sel[j] : j];
+        std::string& out = w.shard(uid);
+        for (uint32_t r = 0; r < count[j]; ++r) {
+            cfio::append_u(out, uid);
+            out += '\t';
+            cfio::append_u(out, fv.ids.ids[items[(size_t)j * N + r]]);
+            out += '\t';
+            cfio::append_g(out, scores[(size_t)j * N + r]);
+            out += '\n';
+        }
+    }
+    w.flush();
+    cf_destroy(ctx);
+    return 0;
+}

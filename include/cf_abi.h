@@ -37,6 +37,8 @@
  *                                  479-499 (its error_aggregator is cf_sgd_error)
  *   cf_svd_fit / cf_svd_matvec     : lanczos() with Axb and orthogonalize_vs_all, svd.cpp:304-505,
  *                                  math.hpp:98-185,805-906
+ *   cf_mf_topn                     : none (the reference saves PREDICT edges only, als.cpp:493-510);
+ *                                  the N best unrated items per user from the fitted factors
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -70,7 +72,7 @@ int cf_device_count(void);
 int cf_create(int device, cf_ctx** out);
 void cf_destroy(cf_ctx* ctx);
 /* Waits for the context's device, then frees its cached HBM workspaces (eigen and predictor
- * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD / SVD++ / SVD); each is
+ * spill paths, the tridiagonal path, the predictor scratch, the knn2 planes, ALS / SGD / SVD++ / SVD / top-N); each is
  * allocated again, at the size its next call plans, when that call runs.  The spill paths
  * size their workspaces from the device's free HBM, so a workspace the predictor left behind
  * shrinks the next eigen call's and costs it waves: call this between stages of a long-lived
@@ -738,6 +740,44 @@ int cf_debug_svd_wave_max(void);
  * T is m x m row-major; a, PT (m x m row-major) and b (m, descending) with T = a diag(b) PT^T.
  * Returns the number of sweeps, or CF_EINVAL. */
 int cf_debug_small_svd(int m, const double* T, double* a, double* b, double* PT);
+
+/* ---- top-N recommendation from fitted factors (no reference counterpart: its programs save only
+ * the PREDICT edges, als.cpp:493-510) ----
+ * For every selected user the N best candidate items by score.  sel_user NULL selects users
+ * 0..n_users-1 (n_sel is ignored); otherwise list j is that of user sel_user[j], j < n_sel.
+ *   candidates of user u : every item i that is not in excl_item[excl_off[u] .. excl_off[u+1]) (a CSR
+ *       over all n_users; any order, repeats allowed; both pointers NULL = no exclusions)
+ *   dot(u, i) = sum over d ascending of U[u,d] V[i,d], on the fp64 matrix cores from a zero
+ *       accumulator, D zero-padded to a multiple of 4
+ *   score = dot + (bias_item[i] + (mean + bias_user[u])); an absent bias is skipped, not added as 0,
+ *       and mean is used only when a bias is given
+ *   a NaN score is never listed and counts in n_nan; -0.0 ranks equal to +0.0 (and is reported as +0.0)
+ * Outputs per selected user j: count[j] = min(N, non-NaN candidates); items[j N .. j N + count[j])
+ * and the matching scores ordered by score descending, ties by ascending item index (the rule of
+ * cf_set_knn2_topk); the tail up to N is UINT32_MAX / 0.0.
+ * A score's bits depend only on its own two rows and biases and there is no floating-point atomic:
+ * a user's list is the same bytes across repeats, for every user-block size, and whichever other
+ * users are selected.  The users run in blocks whose n_items keys per user (a panel in the ALS
+ * workspace) fit a fixed byte budget; cf_set_topn_block forces the users per block (0 = automatic).
+ * CF_ERANGE: D == 0, D > CF_ALS_MAX_D, N > CF_TOPN_MAX_N.  CF_EINVAL: N == 0, exactly one of
+ * excl_off / excl_item NULL, a decreasing excl_off, an excl_item >= n_items, a sel_user >= n_users.
+ * n_users == 0, n_items == 0 or n_sel == 0 with a non-NULL sel_user is a valid call that writes
+ * only count (zeros). */
+#define CF_TOPN_MAX_N 1024
+typedef struct cf_topn_stats {
+    uint32_t blocks;      /* user blocks processed */
+    uint64_t n_nan;       /* candidate scores that were NaN (left out of every list) */
+    float score_ms;       /* device time of the scoring kernels (HIP events) */
+    float select_ms;      /* device time of exclusion, selection and ordering */
+} cf_topn_stats;
+int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
+               const double* bias_user, const double* bias_item, double mean, const uint64_t* excl_off,
+               const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user, uint32_t N, uint32_t* items,
+               double* scores, uint32_t* count, cf_topn_stats* stats);
+int cf_set_topn_block(cf_ctx* ctx, uint32_t users_per_block);
+/* The user and item tile of the scoring kernel (constants of cf_topn.hip; test helpers). */
+int cf_debug_topn_tile_users(void);
+int cf_debug_topn_tile_items(void);
 
 #ifdef __cplusplus
 }
