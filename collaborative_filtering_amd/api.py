@@ -187,6 +187,49 @@ def _csr(row, col, obs, n_rows):
     return off, np.ascontiguousarray(col[perm]), np.ascontiguousarray(obs[perm])
 
 
+def _mf_factors(mats, ns, names, shapes):
+    """The factor matrices of a fit as C-ordered fp64 copies reshaped to (n, D), and D.  D comes
+    from whichever side has vertices (an empty side may come as any empty array)."""
+    mats = [np.array(x, dtype=np.float64, order="C") for x in mats]
+    dims = {a.size // n for a, n in zip(mats, ns) if n}
+    if len(dims) > 1:
+        raise ValueError(f"{names} differ in D")
+    D = dims.pop() if dims else (mats[0].shape[1] if mats[0].ndim == 2 and mats[0].shape[1] else 1)
+    if any(a.size != n * D for a, n in zip(mats, ns)):
+        raise ValueError(f"{shapes} do not hold n_users x D / n_items x D values")
+    return [a.reshape(n, D) for a, n in zip(mats, ns)], D
+
+
+def _mf_csr_pair(user, item, obs, n_users, n_items):
+    """The user CSR and the item CSR of the TRAIN edges, as the six arrays the fits take."""
+    if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
+        raise ValueError("edge index out of range")
+    return _csr(user, item, obs, n_users) + _csr(item, user, obs, n_items)
+
+
+def _mf_nupdates(nupdates, n_users, n_items):
+    if nupdates is None:
+        return [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)]
+    return [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+
+
+def _mf_trace_rows(trace, max_updates, max_supersteps):
+    """One trace row per user superstep, bounded by whichever cap is set."""
+    if not trace:
+        return 0
+    bounds = [(max_supersteps + 1) // 2] if max_supersteps else []
+    if max_updates is not None:
+        bounds.append(int(max_updates) + 1)
+    return min(bounds) if bounds else 0
+
+
+def _mf_validate(validate):
+    if validate is None or not len(validate[0]):
+        return None, None, None
+    return (np.ascontiguousarray(validate[0], dtype=np.uint32), np.ascontiguousarray(validate[1], dtype=np.uint32),
+            np.ascontiguousarray(validate[2], dtype=np.float32))
+
+
 class Context:
     """One device context (cf_ctx) holding the HBM-resident item graph."""
 
@@ -576,20 +619,8 @@ class Context:
         item = np.ascontiguousarray(item, dtype=np.uint32)
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         n_users, n_items = int(n_users), int(n_items)
-        U = np.array(U0, dtype=np.float64, order="C")
-        V = np.array(V0, dtype=np.float64, order="C")
-        # D from whichever side has vertices (an empty side may come as any empty array)
-        dims = {a.size // n for a, n in ((U, n_users), (V, n_items)) if n}
-        if len(dims) > 1:
-            raise ValueError("U0 and V0 differ in D")
-        D = dims.pop() if dims else (U.shape[1] if U.ndim == 2 and U.shape[1] else 1)
-        if U.size != n_users * D or V.size != n_items * D:
-            raise ValueError("U0 / V0 do not hold n_users x D / n_items x D values")
-        U, V = U.reshape(n_users, D), V.reshape(n_items, D)
-        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
-            raise ValueError("edge index out of range")
-        uoff, uitem, uobs = _csr(user, item, obs, n_users)
-        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        (U, V), D = _mf_factors((U0, V0), (n_users, n_items), "U0 and V0", "U0 / V0")
+        uoff, uitem, uobs, ioff, iuser, iobs = _mf_csr_pair(user, item, obs, n_users, n_items)
         du = np.diff(uoff.astype(np.int64)).astype(np.float64)
         di = np.diff(ioff.astype(np.int64)).astype(np.float64)
         od = du if out_degree is None else np.asarray(out_degree, dtype=np.float64)
@@ -603,8 +634,7 @@ class Context:
         ri = np.ascontiguousarray(ri, dtype=np.float64)
         act = (od > 0) if activate_user is None else np.asarray(activate_user) != 0
         act = np.ascontiguousarray(act, dtype=np.uint8)
-        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
-            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        nu = _mf_nupdates(nupdates, n_users, n_items)
         rs = [np.zeros(n_users, np.float32), np.zeros(n_items, np.float32)] if residual is None else \
             [np.array(residual[0], dtype=np.float32), np.array(residual[1], dtype=np.float32)]
         st = _native.AlsStats()
@@ -661,19 +691,8 @@ class Context:
         item = np.ascontiguousarray(item, dtype=np.uint32)
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         n_users, n_items = int(n_users), int(n_items)
-        U = np.array(U0, dtype=np.float64, order="C")
-        V = np.array(V0, dtype=np.float64, order="C")
-        dims = {a.size // n for a, n in ((U, n_users), (V, n_items)) if n}
-        if len(dims) > 1:
-            raise ValueError("U0 and V0 differ in D")
-        D = dims.pop() if dims else (U.shape[1] if U.ndim == 2 and U.shape[1] else 1)
-        if U.size != n_users * D or V.size != n_items * D:
-            raise ValueError("U0 / V0 do not hold n_users x D / n_items x D values")
-        U, V = U.reshape(n_users, D), V.reshape(n_items, D)
-        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
-            raise ValueError("edge index out of range")
-        uoff, uitem, uobs = _csr(user, item, obs, n_users)
-        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        (U, V), D = _mf_factors((U0, V0), (n_users, n_items), "U0 and V0", "U0 / V0")
+        uoff, uitem, uobs, ioff, iuser, iobs = _mf_csr_pair(user, item, obs, n_users, n_items)
         bu = bi = None
         mean = 0.0
         if bias:
@@ -684,22 +703,12 @@ class Context:
             else:
                 mean = float(global_mean)
         act = None if activate_user is None else np.ascontiguousarray(np.asarray(activate_user) != 0, dtype=np.uint8)
-        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
-            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        nu = _mf_nupdates(nupdates, n_users, n_items)
         cap = (1 << 64) - 1 if max_updates is None else int(max_updates)
         max_supersteps = int(max_supersteps)
-        rows = 0
-        if trace:   # one row per user superstep, bounded by whichever cap is set
-            bounds = [(max_supersteps + 1) // 2] if max_supersteps else []
-            if max_updates is not None:
-                bounds.append(int(max_updates) + 1)
-            rows = min(bounds) if bounds else 0
+        rows = _mf_trace_rows(trace, max_updates, max_supersteps)
         tr = np.zeros((max(rows, 1), 2))
-        vu = vi = vo = None
-        if validate is not None and len(validate[0]):
-            vu = np.ascontiguousarray(validate[0], dtype=np.uint32)
-            vi = np.ascontiguousarray(validate[1], dtype=np.uint32)
-            vo = np.ascontiguousarray(validate[2], dtype=np.float32)
+        vu, vi, vo = _mf_validate(validate)
         par = _native.SgdParams(float(lam), float(gamma), float(step_dec), float(tol), float(minval), float(maxval),
                                 mean, cap, max_supersteps)
         st = _native.SgdStats()
@@ -776,19 +785,9 @@ class Context:
         item = np.ascontiguousarray(item, dtype=np.uint32)
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         n_users, n_items = int(n_users), int(n_items)
-        mats = [np.array(x, dtype=np.float64, order="C") for x in (U0, V0, W0, Y0)]
-        ns = (n_users, n_items, n_users, n_items)
-        dims = {a.size // n for a, n in zip(mats, ns) if n}
-        if len(dims) > 1:
-            raise ValueError("U0, V0, W0 and Y0 differ in D")
-        D = dims.pop() if dims else (mats[0].shape[1] if mats[0].ndim == 2 and mats[0].shape[1] else 1)
-        if any(a.size != n * D for a, n in zip(mats, ns)):
-            raise ValueError("U0 / W0 / V0 / Y0 do not hold n_users x D / n_items x D values")
-        U, V, W, Y = (a.reshape(n, D) for a, n in zip(mats, ns))
-        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
-            raise ValueError("edge index out of range")
-        uoff, uitem, uobs = _csr(user, item, obs, n_users)
-        ioff, iuser, iobs = _csr(item, user, obs, n_items)
+        (U, V, W, Y), D = _mf_factors((U0, V0, W0, Y0), (n_users, n_items, n_users, n_items), "U0, V0, W0 and Y0",
+                                      "U0 / W0 / V0 / Y0")
+        uoff, uitem, uobs, ioff, iuser, iobs = _mf_csr_pair(user, item, obs, n_users, n_items)
         poff = pitem = None
         if implicit is not None and len(implicit[0]):
             pu = np.ascontiguousarray(implicit[0], dtype=np.uint32)
@@ -803,22 +802,12 @@ class Context:
         else:
             mean = float(global_mean)
         act = None if activate_user is None else np.ascontiguousarray(np.asarray(activate_user) != 0, dtype=np.uint8)
-        nu = [np.zeros(n_users, np.uint32), np.zeros(n_items, np.uint32)] if nupdates is None else \
-            [np.array(nupdates[0], dtype=np.uint32), np.array(nupdates[1], dtype=np.uint32)]
+        nu = _mf_nupdates(nupdates, n_users, n_items)
         cap = (1 << 64) - 1 if max_updates is None else int(max_updates)
         max_supersteps = int(max_supersteps)
-        rows = 0
-        if trace:   # one row per user superstep, bounded by whichever cap is set
-            bounds = [(max_supersteps + 1) // 2] if max_supersteps else []
-            if max_updates is not None:
-                bounds.append(int(max_updates) + 1)
-            rows = min(bounds) if bounds else 0
+        rows = _mf_trace_rows(trace, max_updates, max_supersteps)
         tr = np.zeros((max(rows, 1), 2))
-        vu = vi = vo = None
-        if validate is not None and len(validate[0]):
-            vu = np.ascontiguousarray(validate[0], dtype=np.uint32)
-            vi = np.ascontiguousarray(validate[1], dtype=np.uint32)
-            vo = np.ascontiguousarray(validate[2], dtype=np.float32)
+        vu, vi, vo = _mf_validate(validate)
         par = _native.SvdppParams(user_bias_step, user_bias_reg, item_bias_step, item_bias_reg, user_factor_step,
                                   user_factor_reg, item_factor_step, item_factor_reg, item_factor2_step,
                                   item_factor2_reg, float(step_dec), float(minval), float(maxval), mean, cap,

@@ -28,7 +28,8 @@
 // Determinism rule: the class, the split points and every summation order of a vertex depend on
 // its own degree only -- never on the launch, the active list or other vertices -- and there is
 // no floating-point atomic, so a vertex's new factor is the same bits whichever other vertices
-// are active and however often a fit is repeated.
+// are active and however often a fit is repeated.  (The Gram kernels below implement the rule
+// for ALS; SGD and SVD++ share one implementation of it, cf_mf_reduce.h.)
 //
 // The Gram of one wave: D is padded to DP = 8 / 16 / 32 / 64 and lane l owns the TS x TS block
 // (TS = DP / 8) at block row l >> 3, block column l & 7 of A, in registers; neighbour rows are
@@ -43,7 +44,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 #include "cf_internal.h"
 #include "cf_ldlt.hpp"
@@ -335,17 +335,10 @@ void carve_fit(Carver& c, FitLayout& f, uint32_t n_users, uint32_t n_items, uint
     const uint32_t n[2] = {n_users, n_items};
     for (int k = 0; k < 2; ++k) {
         AlsSide& s = f.side[k];
-        s.n = n[k];
-        s.off = c.take<uint64_t>((size_t)n[k] + 1);
-        s.nbr = c.take<uint32_t>(nnz);
-        s.obs = c.take<float>(nnz);
-        s.src = c.take<uint32_t>(nnz);
+        carve_side(c, s, n[k], nnz);
         s.F = c.take<double>((size_t)n[k] * D);
         s.reg = c.take<double>(n[k]);
-        s.nupd = c.take<uint32_t>(n[k]);
         s.resid = c.take<float>(n[k]);
-        s.flag = c.take<uint8_t>(n[k]);
-        s.active = c.take<uint8_t>(n[k]);
     }
     const size_t nmax = std::max(n_users, n_items);
     carve_lists(c, f.lists, nmax, seg_cap);
@@ -400,14 +393,7 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     const uint64_t seg_cap = std::max(total_segments(n_users, user_off), n_items ? total_segments(n_items, item_off) : 0);
     if (seg_cap > 0xffffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_als_fit: too many segments");
     FitLayout f{};
-    {
-        Carver size;
-        carve_fit(size, f, n_users, n_items, nnz, (int)D, seg_cap);
-        CF_TRY(als_reserve(ctx, size.pos));
-        Carver c;
-        c.base = static_cast<char*>(ctx->d_als);
-        carve_fit(c, f, n_users, n_items, nnz, (int)D, seg_cap);
-    }
+    CF_TRY(carve_workspace(ctx, [&](Carver& c) { carve_fit(c, f, n_users, n_items, nnz, (int)D, seg_cap); }));
     MfEvents<3> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
     hipStream_t st = nullptr;
@@ -423,22 +409,10 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     for (int k = 0; k < 2; ++k) {
         if (n[k] == 0) continue;
         const AlsSide& s = f.side[k];
-        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.off, h_off[k], sizeof(uint64_t) * ((size_t)n[k] + 1), hipMemcpyHostToDevice));
-        if (nnz) {
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.nbr, h_nbr[k], sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.obs, h_obs[k], sizeof(float) * nnz, hipMemcpyHostToDevice));
-            std::vector<uint32_t> src(nnz);
-            for (uint32_t v = 0; v < n[k]; ++v)
-                for (uint64_t e = h_off[k][v]; e < h_off[k][v + 1]; ++e) src[e] = v;
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-        }
+        CF_TRY(upload_side(ctx, s, nnz, h_off[k], h_nbr[k], h_obs[k], h_nupd[k], k == 0 ? activate_user : nullptr, k == 0));
         CF_HIP_CHECK(ctx, hipMemcpy(s.F, h_F[k], sizeof(double) * (size_t)n[k] * D, hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemcpy((void*)s.reg, h_reg[k], sizeof(double) * n[k], hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(s.nupd, h_nupd[k], sizeof(uint32_t) * n[k], hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemcpy(s.resid, h_res[k], sizeof(float) * n[k], hipMemcpyHostToDevice));
-        if (k == 0 && activate_user) CF_HIP_CHECK(ctx, hipMemcpy(s.flag, activate_user, n[k], hipMemcpyHostToDevice));
-        else CF_HIP_CHECK(ctx, hipMemset(s.flag, k == 0 ? 1 : 0, n[k]));
-        CF_HIP_CHECK(ctx, hipMemset(s.active, 0, n[k]));
     }
     CF_HIP_CHECK(ctx, hipMemset(f.not_pd, 0, sizeof(unsigned long long)));
 
@@ -456,11 +430,8 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         CF_HIP_CHECK(ctx, hipGetLastError());
         CF_HIP_CHECK(ctx, hipMemcpy(rec, f.lists.record, sizeof(rec), hipMemcpyDeviceToHost));   // waits for the stream
         if (supersteps) {
-            float a = 0.0f, b = 0.0f;
-            (void)hipEventElapsedTime(&a, evs.e[0], evs.e[1]);
-            (void)hipEventElapsedTime(&b, evs.e[1], evs.e[2]);
-            update_ms += a;
-            scatter_ms += b;
+            update_ms += elapsed(evs.e[0], evs.e[1]);
+            scatter_ms += elapsed(evs.e[1], evs.e[2]);
         }
         const uint64_t n_active = (uint64_t)rec[0] + rec[1] + rec[2];
         if (n_active == 0) break;                                   // the run ends when no vertex is active

@@ -1,12 +1,15 @@
-// cf_mf_common.h -- what the matrix-factorization files (cf_als.hip, cf_sgd.hip) share: the
-// degree cuts, the scan compaction of one side's flags into per-class active lists, the
-// dot-product group, the fixed block reduction, and the host helpers around the context-owned
-// workspace (one allocation, ctx->d_als, carved per call).  Everything has internal linkage.
+// cf_mf_common.h -- what the matrix-factorization files (cf_als.hip, cf_sgd.hip, cf_svdpp.hip)
+// share: the degree cuts, the scan compaction of one side's flags into per-class active lists,
+// the dot-product group, the fixed block reduction, and the host helpers of the fits: argument
+// checks, the context-owned workspace (one allocation, ctx->d_als, carved per call) and the
+// uploads of a side and of the validation edges.  The vertex reduction of SGD and SVD++ is in
+// cf_mf_reduce.h.  Everything has internal linkage.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -266,6 +269,83 @@ inline int als_reserve(cf_ctx* ctx, size_t bytes) {
     return CF_OK;
 }
 
+// Runs carve twice: the size pass, then, with the workspace reserved, over ctx->d_als.
+template <class F>
+int carve_workspace(cf_ctx* ctx, F carve) {
+    Carver size;
+    carve(size);
+    CF_TRY(als_reserve(ctx, size.pos));
+    Carver c;
+    c.base = static_cast<char*>(ctx->d_als);
+    carve(c);
+    return CF_OK;
+}
+
+// The part of one side that every fit keeps (AlsSide, SgdSide, PpSide): its CSR with the owner
+// of each edge, the update counts and the flags.
+template <class Side>
+void carve_side(Carver& c, Side& s, uint32_t n, uint64_t nnz) {
+    s.n = n;
+    s.off = c.take<uint64_t>((size_t)n + 1);
+    s.nbr = c.take<uint32_t>(nnz);
+    s.obs = c.take<float>(nnz);
+    s.src = c.take<uint32_t>(nnz);
+    s.nupd = c.take<uint32_t>(n);
+    s.flag = c.take<uint8_t>(n);
+    s.active = c.take<uint8_t>(n);
+}
+
+// Uploads that part of a side with n > 0 vertices.  flag = activate, or flag_fill everywhere
+// where activate is NULL.
+template <class Side>
+int upload_side(cf_ctx* ctx, const Side& s, uint64_t nnz, const uint64_t* off, const uint32_t* nbr, const float* obs,
+                const uint32_t* nupd, const uint8_t* activate, int flag_fill) {
+    CF_HIP_CHECK(ctx, hipMemcpy((void*)s.off, off, sizeof(uint64_t) * ((size_t)s.n + 1), hipMemcpyHostToDevice));
+    if (nnz) {
+        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.nbr, nbr, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.obs, obs, sizeof(float) * nnz, hipMemcpyHostToDevice));
+        std::vector<uint32_t> src(nnz);
+        for (uint32_t v = 0; v < s.n; ++v)
+            for (uint64_t e = off[v]; e < off[v + 1]; ++e) src[e] = v;
+        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+    }
+    CF_HIP_CHECK(ctx, hipMemcpy(s.nupd, nupd, sizeof(uint32_t) * s.n, hipMemcpyHostToDevice));
+    if (activate) CF_HIP_CHECK(ctx, hipMemcpy(s.flag, activate, s.n, hipMemcpyHostToDevice));
+    else CF_HIP_CHECK(ctx, hipMemset(s.flag, flag_fill, s.n));
+    CF_HIP_CHECK(ctx, hipMemset(s.active, 0, s.n));
+    return CF_OK;
+}
+
+// The VALIDATE edges of a traced fit on the device.
+struct MfVal {
+    uint32_t* user;
+    uint32_t* item;
+    float* obs;
+};
+
+inline void carve_val(Carver& c, MfVal& v, uint64_t n) {
+    v.user = c.take<uint32_t>(n);
+    v.item = c.take<uint32_t>(n);
+    v.obs = c.take<float>(n);
+}
+
+inline int upload_val(cf_ctx* ctx, const MfVal& v, uint64_t n, const uint32_t* user, const uint32_t* item,
+                      const float* obs) {
+    if (n == 0) return CF_OK;
+    CF_HIP_CHECK(ctx, hipMemcpy(v.user, user, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(v.item, item, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(v.obs, obs, sizeof(float) * n, hipMemcpyHostToDevice));
+    return CF_OK;
+}
+
+inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kAT - 1) / kAT); }
+
+inline float elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, a, b);
+    return ms;
+}
+
 inline uint64_t total_segments(uint32_t n, const uint64_t* off) {
     uint64_t segs = 0;
     for (uint32_t v = 0; v < n; ++v) {
@@ -339,6 +419,25 @@ inline int check_two_csr(cf_ctx* ctx, const char* fn, uint32_t n_users, uint32_t
     return CF_OK;
 }
 
+// The two checks cf_sgd_fit and cf_svdpp_fit share beyond check_two_csr(): a cap is set, and the
+// VALIDATE edges of a traced fit are in range.
+inline int check_caps(cf_ctx* ctx, const char* fn, uint64_t max_updates, uint32_t max_supersteps) {
+    if (max_updates == std::numeric_limits<uint64_t>::max() && max_supersteps == 0)
+        return cf_set_error(ctx, CF_EINVAL, std::string(fn) +
+                                                ": neither max_updates nor max_supersteps is set (the run would never end)");
+    return CF_OK;
+}
+
+inline int check_validation(cf_ctx* ctx, const char* fn, uint64_t n, const uint32_t* user, const uint32_t* item,
+                            const float* obs, uint32_t n_users, uint32_t n_items) {
+    if (n == 0) return CF_OK;
+    if (!user || !item || !obs) return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": null validation array");
+    for (uint64_t e = 0; e < n; ++e)
+        if (user[e] >= n_users || item[e] >= n_items)
+            return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": validation index out of range");
+    return CF_OK;
+}
+
 inline int check_pairs(cf_ctx* ctx, const char* fn, uint64_t n, const uint32_t* user, const uint32_t* item,
                        const double* U, const double* V, uint32_t D, uint32_t n_users, uint32_t n_items) {
     if (D == 0) return cf_set_error(ctx, CF_EINVAL, std::string(fn) + ": D = 0");
@@ -366,9 +465,7 @@ struct PairLayout {
 inline int upload_pairs(cf_ctx* ctx, PairLayout& p, uint64_t n, const uint32_t* user, const uint32_t* item,
                         const float* obs, uint32_t nu, uint32_t ni, uint32_t D, const double* U, const double* V,
                         size_t n_out, const double* bu = nullptr, const double* bi = nullptr) {
-    for (int pass = 0; pass < 2; ++pass) {
-        Carver c;
-        if (pass) c.base = static_cast<char*>(ctx->d_als);
+    CF_TRY(carve_workspace(ctx, [&](Carver& c) {
         p.user = c.take<uint32_t>(n);
         p.item = c.take<uint32_t>(n);
         p.obs = c.take<float>(n);
@@ -377,8 +474,7 @@ inline int upload_pairs(cf_ctx* ctx, PairLayout& p, uint64_t n, const uint32_t* 
         p.out = c.take<double>(n_out);
         p.bu = bu ? c.take<double>(nu) : nullptr;
         p.bi = bi ? c.take<double>(ni) : nullptr;
-        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
-    }
+    }));
     CF_HIP_CHECK(ctx, hipMemcpy(p.user, user, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     CF_HIP_CHECK(ctx, hipMemcpy(p.item, item, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     if (obs) CF_HIP_CHECK(ctx, hipMemcpy(p.obs, obs, sizeof(float) * n, hipMemcpyHostToDevice));

@@ -23,33 +23,22 @@
 // reduction of one side reads about nnz (8 D + 8) bytes and does 4 nnz D flops (dot and axpy):
 // bound by the row gathers.
 //
-// One wave works on eight edges at a time: lane group g = lane >> 3 (kG = 8 lanes) takes edges
-// g, g + 8, .. of the wave's range, lane sl of the group holds elements sl, sl + 8, .. of the
-// neighbour's row and of the vertex's own row in registers (coalesced 64-byte pieces of a row).
-// A row is used by exactly one group, so it is gathered straight into registers; ALS stages rows
-// in LDS because every lane of its wave needs every row, which is not the case here.
+// The reduction runs on the shared skeleton of cf_mf_reduce.h (lane mapping, the low / mid / high
+// classes on the vertex's TRAIN degree, every summation order: the determinism rule of DESIGN
+// 3.12); this file supplies SgdOp, what one edge adds and how the sums become deltas.  A row is
+// used by exactly one lane group, so it is gathered straight into registers; ALS stages rows in
+// LDS because every lane of its wave needs every row, which is not the case here.
 // The dot product is edge_err(): the same fma order over d and the same butterfly as
 // group_dot(), called with (U row, V row) from both sides, so err_e has the same float bits on
 // the user side and the item side and both agree on every threshold.
-//
-// Work is shaped by the vertex's TRAIN degree with the cuts of ALS (cf_mf_common.h):
-//   low   one wave per vertex; mid  one workgroup per vertex, its waves take contiguous quarters
-//   and their partials are summed in wave order in LDS; high  segments of kSeg edges, one
-//   workgroup per segment (as mid) writes D + 2 partial sums to an HBM workspace and one wave per
-//   vertex adds them in segment order.
-// Determinism rule: the class, the split points and every summation order of a
-// vertex depend on its own degree only; an edge the predicate rejects adds nothing and does not
-// move the others; no floating-point atomics (the NaN and message counters are integer atomics).
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <limits>
-#include <vector>
 
 #include "cf_internal.h"
-#include "cf_mf_common.h"
+#include "cf_mf_reduce.h"
 
 namespace {
 
@@ -91,198 +80,73 @@ __device__ __forceinline__ float edge_err(const double (&u)[NJ], const double (&
     return (float)(p - (double)obs);
 }
 
-template <int NJ>
-__device__ __forceinline__ void load_row(double (&x)[NJ], const double* __restrict__ row, int D, int sl) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int d = sl + kG * j;
-        x[j] = d < D ? row[d] : 0.0;
-    }
-}
-
-// The partial sums of one wave: lane (g, sl) holds its group's part until reduce_groups().
-template <int NJ>
-struct Acc {
-    double s[NJ];   // sum err x, elements sl + 8 j
-    double e;       // sum err (the bias part)
-    uint32_t cnt;   // accepted edges
-    uint32_t nan;   // NaN errors met (user side)
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) s[j] = 0.0;
-        e = 0.0;
-        cnt = 0;
-        nan = 0;
-    }
-    // fixed butterfly over the eight groups: afterwards every lane holds the wave's sums
-    __device__ __forceinline__ void reduce_groups() {
-#pragma unroll
-        for (int o = kG; o < 64; o <<= 1) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) s[j] += __shfl_xor(s[j], o);
-            e += __shfl_xor(e, o);
-            cnt += __shfl_xor(cnt, o);
-            nan += __shfl_xor(nan, o);
-        }
-    }
-};
-
-// acc += the edges [p0, p1) of vertex v (side s; ITEM: v is an item and the neighbours are
-// users of side o).  Called by a whole wave.
-template <int NJ, bool ITEM>
-__device__ __forceinline__ void wave_accumulate(Acc<NJ>& acc, const double (&own)[NJ], double own_bias, const SgdSide& s,
-                                                const SgdSide& o, const SgdArgs& a, uint64_t p0, uint64_t p1,
-                                                int lane) {
-    const int g = lane >> 3, sl = lane & (kG - 1);
-    const bool bias = s.b != nullptr;
-    for (uint64_t base = p0; base < p1; base += 64 / kG) {
-        const uint64_t e = base + g;
-        if (e >= p1) continue;                    // whole groups
-        const uint32_t w = s.nbr[e];
-        if (ITEM && !o.active[w]) continue;       // the user did not run: no message on this edge
-        double x[NJ];
-        load_row<NJ>(x, o.F + (size_t)w * a.D, a.D, sl);
-        const double ob = bias ? o.b[w] : 0.0;
-        const float err = ITEM ? edge_err<NJ>(x, own, bias, a.mean, ob, own_bias, s.obs[e], a.minval, a.maxval)
-                               : edge_err<NJ>(own, x, bias, a.mean, own_bias, ob, s.obs[e], a.minval, a.maxval);
-        if (!ITEM && err != err) acc.nan += sl == 0;
-        if (ITEM && !(fabs((double)err) > a.tol)) continue;
-        const double ed = (double)err;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc.s[j] = fma(ed, x[j], acc.s[j]);
-        acc.e += ed;
-        acc.cnt += 1;
-    }
-}
-
 __device__ __forceinline__ double sgd_delta(double sum, double cnt, double own, const SgdArgs& a) {
     return -a.gamma * (sum + cnt * a.lambda * own);
 }
 
-// counters: [0] NaN errors, [1] messages (edges the item-side predicate accepted)
+// The policy of the reduction of side s (ITEM: s holds the items and the neighbours are users of
+// side o): D sums err x, the scalar sum err (the bias part), and
+//   delta[v] = -gamma (sum + cnt lambda own_v)
 template <bool ITEM>
-__device__ __forceinline__ void count_events(unsigned long long* counters, uint32_t nan, double cnt) {
-    if (!ITEM && nan) atomicAdd(&counters[0], (unsigned long long)nan);
-    if (ITEM && cnt > 0.0) atomicAdd(&counters[1], (unsigned long long)cnt);
-}
-
-// low class: one wave per vertex.
-template <int NJ, bool ITEM>
-__global__ __launch_bounds__(kAT) void sgd_low_kernel(SgdSide s, SgdSide o, SgdArgs a, const uint32_t* __restrict__ list,
-                                                     uint32_t count_v, unsigned long long* counters) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count_v) return;   // whole waves leave; no block barrier below
-    const uint32_t v = list[j];
-    const int sl = lane & (kG - 1);
-    double own[NJ];
-    load_row<NJ>(own, s.F + (size_t)v * a.D, a.D, sl);
-    const double own_bias = s.b ? s.b[v] : 0.0;
-    Acc<NJ> acc;
-    acc.clear();
-    wave_accumulate<NJ, ITEM>(acc, own, own_bias, s, o, a, s.off[v], s.off[v + 1], lane);
-    acc.reduce_groups();
-    if (lane < kG) {
+struct SgdOp {
+    static constexpr int NS = 1;
+    static constexpr bool kCountNan = !ITEM;
+    SgdSide s, o;
+    SgdArgs a;
+    template <int NJ>
+    struct Own {
+        double row[NJ];
+        double bias;
+    };
+    __host__ __device__ int dim() const { return a.D; }
+    __device__ __forceinline__ uint64_t begin(uint32_t v) const { return s.off[v]; }
+    __device__ __forceinline__ uint64_t end(uint32_t v) const { return s.off[v + 1]; }
+    template <int NJ>
+    __device__ __forceinline__ void load_own(Own<NJ>& own, uint32_t v, int sl) const {
+        load_row<NJ>(own.row, s.F + (size_t)v * a.D, a.D, sl);
+        own.bias = s.b ? s.b[v] : 0.0;
+    }
+    template <int NJ>
+    __device__ __forceinline__ void edge(Acc<NJ, NS>& acc, const Own<NJ>& own, uint64_t e, int sl) const {
+        const bool bias = s.b != nullptr;
+        const uint32_t w = s.nbr[e];
+        if (ITEM && !o.active[w]) return;         // the user did not run: no message on this edge
+        double x[NJ];
+        load_row<NJ>(x, o.F + (size_t)w * a.D, a.D, sl);
+        const double ob = bias ? o.b[w] : 0.0;
+        const float err = ITEM ? edge_err<NJ>(x, own.row, bias, a.mean, ob, own.bias, s.obs[e], a.minval, a.maxval)
+                               : edge_err<NJ>(own.row, x, bias, a.mean, own.bias, ob, s.obs[e], a.minval, a.maxval);
+        if (!ITEM && err != err) acc.nan += sl == 0;
+        if (ITEM && !(fabs((double)err) > a.tol)) return;
+        const double ed = (double)err;
 #pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int d = sl + kG * jj;
-            if (d < a.D) s.dF[(size_t)v * a.D + d] = sgd_delta(acc.s[jj], (double)acc.cnt, own[jj], a);
-        }
+        for (int j = 0; j < NJ; ++j) acc.s[j] = fma(ed, x[j], acc.s[j]);
+        acc.x[0] += ed;
+        acc.cnt += 1;
     }
-    if (lane == 0) {
-        if (s.b) s.db[v] = sgd_delta(acc.e, (double)acc.cnt, own_bias, a);
-        count_events<ITEM>(counters, acc.nan, (double)acc.cnt);
+    __device__ __forceinline__ void scalar(uint32_t v, double own_bias, double e, double cnt,
+                                           unsigned long long* counters) const {
+        if (s.b) s.db[v] = sgd_delta(e, cnt, own_bias, a);
+        if (ITEM && cnt > 0.0) atomicAdd(&counters[1], (unsigned long long)cnt);   // messages
     }
-}
-
-constexpr int kSlotMax = CF_ALS_MAX_D + 2;   // D sums, the bias sum, the count
-
-// mid class (SEGMENT = false): one workgroup per vertex.  high class (SEGMENT = true): one
-// workgroup per (vertex, segment); its D + 2 partial sums go to workspace slot blockIdx.x.
-template <int NJ, bool ITEM, bool SEGMENT>
-__global__ __launch_bounds__(kAT) void sgd_group_kernel(SgdSide s, SgdSide o, SgdArgs a, const uint32_t* __restrict__ list,
-                                                       const uint32_t* __restrict__ seg_index, double* ws,
-                                                       unsigned long long* counters) {
-    __shared__ double part[kWaves][kSlotMax];
-    __shared__ double tot[kSlotMax];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sl = lane & (kG - 1);
-    const int D = a.D;
-    const uint32_t v = list[blockIdx.x];
-    uint64_t p0 = s.off[v];
-    uint64_t len = s.off[v + 1] - p0;
-    if (SEGMENT) {
-        const uint64_t first = (uint64_t)seg_index[blockIdx.x] * kSeg;
-        p0 += first;
-        len = len - first < (uint64_t)kSeg ? len - first : (uint64_t)kSeg;
+    __device__ __forceinline__ void finish_elem(uint32_t v, int d, double sum, const double*, double cnt) const {
+        s.dF[(size_t)v * a.D + d] = sgd_delta(sum, cnt, s.F[(size_t)v * a.D + d], a);
     }
-    const uint64_t chunk = (len + kWaves - 1) / kWaves;
-    const uint64_t b = std::min(len, wave * chunk), e = std::min(len, (wave + 1) * chunk);
-    double own[NJ];
-    load_row<NJ>(own, s.F + (size_t)v * D, D, sl);
-    const double own_bias = s.b ? s.b[v] : 0.0;
-    Acc<NJ> acc;
-    acc.clear();
-    wave_accumulate<NJ, ITEM>(acc, own, own_bias, s, o, a, p0 + b, p0 + e, lane);
-    acc.reduce_groups();
-    if (lane < kG) {
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int d = sl + kG * jj;
-            if (d < D) part[wave][d] = acc.s[jj];
-        }
+    __device__ __forceinline__ void finish_scalar(uint32_t v, const double* x, double cnt,
+                                                  unsigned long long* counters) const {
+        scalar(v, s.b ? s.b[v] : 0.0, x[0], cnt, counters);
     }
-    if (lane == 0) {
-        part[wave][D] = acc.e;
-        part[wave][D + 1] = (double)acc.cnt;
-        count_events<ITEM>(counters, acc.nan, 0.0);
+    template <int NJ>
+    __device__ __forceinline__ void finish_elem_own(const Own<NJ>& own, int jj, uint32_t v, int d, double sum,
+                                                    const double*, double cnt) const {
+        s.dF[(size_t)v * a.D + d] = sgd_delta(sum, cnt, own.row[jj], a);
     }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < D + 2) {   // partials summed in wave order
-        double sum = part[0][t];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) sum += part[w][t];
-        if (SEGMENT) ws[(size_t)blockIdx.x * (D + 2) + t] = sum;
-        else tot[t] = sum;
+    template <int NJ>
+    __device__ __forceinline__ void finish_scalar_own(const Own<NJ>& own, uint32_t v, const double* x, double cnt,
+                                                      unsigned long long* counters) const {
+        scalar(v, own.bias, x[0], cnt, counters);
     }
-    if (SEGMENT) return;
-    __syncthreads();
-    const double cnt = tot[D + 1];
-    if (t < D) s.dF[(size_t)v * D + t] = sgd_delta(tot[t], cnt, s.F[(size_t)v * D + t], a);
-    if (t == 0) {
-        if (s.b) s.db[v] = sgd_delta(tot[D], cnt, own_bias, a);
-        count_events<ITEM>(counters, 0, cnt);
-    }
-}
-
-// high class, second pass: one wave per vertex adds its segments' partials in segment order.
-template <bool ITEM>
-__global__ __launch_bounds__(kAT) void sgd_finish_kernel(SgdSide s, SgdArgs a, const uint32_t* __restrict__ list,
-                                                        const uint32_t* __restrict__ base, uint32_t count_v,
-                                                        const double* __restrict__ ws, unsigned long long* counters) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count_v) return;
-    const uint32_t v = list[j];
-    const int D = a.D, n = D + 2;
-    const uint64_t deg = s.off[v + 1] - s.off[v];
-    const uint32_t nseg = (uint32_t)((deg + kSeg - 1) / kSeg);
-    const double* slot = ws + (size_t)base[j] * n;
-    double cnt = 0.0, esum = 0.0;   // every lane adds these two itself, in the same order
-    for (uint32_t q = 0; q < nseg; ++q) {
-        esum = q ? esum + slot[(size_t)q * n + D] : slot[D];
-        cnt = q ? cnt + slot[(size_t)q * n + D + 1] : slot[D + 1];
-    }
-    for (int d = lane; d < D; d += 64) {
-        double sum = slot[d];
-        for (uint32_t q = 1; q < nseg; ++q) sum += slot[(size_t)q * n + d];
-        s.dF[(size_t)v * D + d] = sgd_delta(sum, cnt, s.F[(size_t)v * D + d], a);
-    }
-    if (lane == 0) {
-        if (s.b) s.db[v] = sgd_delta(esum, cnt, s.b[v], a);
-        count_events<ITEM>(counters, 0, cnt);
-    }
-}
+};
 
 // apply: F += dF, b += db, nupdates += 1 for the active vertices of one side.
 __global__ __launch_bounds__(kAT) void sgd_commit_kernel(SgdSide s, int D) {
@@ -297,19 +161,6 @@ __global__ __launch_bounds__(kAT) void sgd_commit_kernel(SgdSide s, int D) {
     }
 }
 
-// scatter (sgd.cpp:320-329): every edge of an active vertex signals its other end while that
-// has updates left.  The flag stores are plain and all write the same value.
-__global__ __launch_bounds__(kAT) void sgd_signal_kernel(const uint32_t* __restrict__ src, const uint32_t* __restrict__ nbr,
-                                                        uint64_t nnz, const uint8_t* __restrict__ active,
-                                                        const uint32_t* __restrict__ nupd_o, uint8_t* flag_o,
-                                                        uint64_t max_updates) {
-    const uint64_t e = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (e >= nnz) return;
-    if (!active[src[e]]) return;
-    const uint32_t w = nbr[e];
-    if ((uint64_t)nupd_o[w] < max_updates) flag_o[w] = 1;
-}
-
 // ---- host ---------------------------------------------------------------------------------
 
 struct SgdLayout {
@@ -317,9 +168,7 @@ struct SgdLayout {
     AlsLists lists[2];
     double* ws;
     unsigned long long* counters;
-    uint32_t* vuser;
-    uint32_t* vitem;
-    float* vobs;
+    MfVal val;
     double* partial;   // error block partials, then {train, validate} sums
     double* sums;
     uint32_t seg_cap;
@@ -330,63 +179,30 @@ void carve_sgd(Carver& c, SgdLayout& f, uint32_t n_users, uint32_t n_items, uint
     const uint32_t n[2] = {n_users, n_items};
     for (int k = 0; k < 2; ++k) {
         SgdSide& s = f.side[k];
-        s.n = n[k];
-        s.off = c.take<uint64_t>((size_t)n[k] + 1);
-        s.nbr = c.take<uint32_t>(nnz);
-        s.obs = c.take<float>(nnz);
-        s.src = c.take<uint32_t>(nnz);
+        carve_side(c, s, n[k], nnz);
         s.F = c.take<double>((size_t)n[k] * D);
         s.dF = c.take<double>((size_t)n[k] * D);
         s.b = bias ? c.take<double>(n[k]) : nullptr;
         s.db = bias ? c.take<double>(n[k]) : nullptr;
-        s.nupd = c.take<uint32_t>(n[k]);
-        s.flag = c.take<uint8_t>(n[k]);
-        s.active = c.take<uint8_t>(n[k]);
         carve_lists(c, f.lists[k], n[k], seg_cap);
     }
-    f.ws = c.take<double>((size_t)seg_cap * (D + 2));
+    f.ws = c.take<double>((size_t)seg_cap * (D + 2));   // D sums, the bias sum, the count
     f.counters = c.take<unsigned long long>(2);
-    f.vuser = c.take<uint32_t>(trace ? n_val : 0);
-    f.vitem = c.take<uint32_t>(trace ? n_val : 0);
-    f.vobs = c.take<float>(trace ? n_val : 0);
+    carve_val(c, f.val, n_val);
     f.partial = c.take<double>(trace ? error_blocks(std::max(nnz, n_val)) : 0);
     f.sums = c.take<double>(2);
     f.seg_cap = (uint32_t)seg_cap;
 }
 
-template <int NJ, bool ITEM>
-void launch_reduce_t(const SgdLayout& f, const SgdArgs& a, const uint32_t rec[4], hipStream_t st) {
-    const int k = ITEM ? 1 : 0;
-    const SgdSide& s = f.side[k];
-    const SgdSide& o = f.side[1 - k];
-    const AlsLists& L = f.lists[k];
-    if (rec[0])
-        hipLaunchKernelGGL((sgd_low_kernel<NJ, ITEM>), dim3((rec[0] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, o, a,
-                           (const uint32_t*)L.low, rec[0], f.counters);
-    if (rec[1])
-        hipLaunchKernelGGL((sgd_group_kernel<NJ, ITEM, false>), dim3(rec[1]), dim3(kAT), 0, st, s, o, a,
-                           (const uint32_t*)L.mid, (const uint32_t*)nullptr, (double*)nullptr, f.counters);
-    if (rec[2]) {
-        hipLaunchKernelGGL((sgd_group_kernel<NJ, ITEM, true>), dim3(rec[3]), dim3(kAT), 0, st, s, o, a,
-                           (const uint32_t*)L.seg_vertex, (const uint32_t*)L.seg_index, f.ws, f.counters);
-        hipLaunchKernelGGL(sgd_finish_kernel<ITEM>, dim3((rec[2] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, a,
-                           (const uint32_t*)L.high, (const uint32_t*)L.high_base, rec[2], (const double*)f.ws, f.counters);
-    }
-}
-
 template <bool ITEM>
 void launch_reduce(const SgdLayout& f, const SgdArgs& a, const uint32_t rec[4], hipStream_t st) {
-    const int D = a.D;
-    if (D <= 8) launch_reduce_t<1, ITEM>(f, a, rec, st);
-    else if (D <= 16) launch_reduce_t<2, ITEM>(f, a, rec, st);
-    else if (D <= 24) launch_reduce_t<3, ITEM>(f, a, rec, st);
-    else if (D <= 32) launch_reduce_t<4, ITEM>(f, a, rec, st);
-    else launch_reduce_t<8, ITEM>(f, a, rec, st);
+    const int k = ITEM ? 1 : 0;
+    launch_reduce(SgdOp<ITEM>{f.side[k], f.side[1 - k], a}, f.lists[k], rec, f.ws, f.counters, st);
 }
 
 void launch_commit(const SgdSide& s, int D, hipStream_t st) {
     const uint64_t total = (uint64_t)s.n * D;
-    if (total) hipLaunchKernelGGL(sgd_commit_kernel, dim3((unsigned)((total + kAT - 1) / kAT)), dim3(kAT), 0, st, s, D);
+    if (total) hipLaunchKernelGGL(sgd_commit_kernel, dim3(blocks_for(total)), dim3(kAT), 0, st, s, D);
 }
 
 // the edges of side `from` signal side `to`, then `to`'s flags are compacted into its lists
@@ -394,15 +210,9 @@ void launch_signal(const SgdLayout& f, int from, uint64_t nnz, uint64_t max_upda
     const SgdSide& s = f.side[from];
     const SgdSide& t = f.side[1 - from];
     if (nnz && t.n)
-        hipLaunchKernelGGL(sgd_signal_kernel, dim3((unsigned)((nnz + kAT - 1) / kAT)), dim3(kAT), 0, st, s.src, s.nbr, nnz,
-                           (const uint8_t*)s.active, (const uint32_t*)t.nupd, t.flag, max_updates);
+        hipLaunchKernelGGL(mf_signal_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, s.src, s.nbr, nnz,
+                           (const uint8_t*)s.active, (const uint32_t*)t.nupd, t.flag, max_updates, true);
     launch_compact(t, f.lists[1 - from], st);
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
 }
 
 }  // namespace
@@ -421,24 +231,17 @@ extern "C" int cf_sgd_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     uint64_t nnz = 0;
     CF_TRY(check_two_csr(ctx, "cf_sgd_fit", n_users, n_items, D, user_off, user_item, user_obs, item_off, item_user,
                          item_obs, &nnz));
-    if (params->max_updates == std::numeric_limits<uint64_t>::max() && params->max_supersteps == 0)
-        return cf_set_error(ctx, CF_EINVAL,
-                            "cf_sgd_fit: neither max_updates nor max_supersteps is set (the run would never end)");
+    CF_TRY(check_caps(ctx, "cf_sgd_fit", params->max_updates, params->max_supersteps));
     if ((bias_user == nullptr) != (bias_item == nullptr))
         return cf_set_error(ctx, CF_EINVAL, "cf_sgd_fit: exactly one bias array is NULL");
     if ((n_users && (!U || !nupdates_user)) || (n_items && (!V || !nupdates_item)))
         return cf_set_error(ctx, CF_EINVAL, "cf_sgd_fit: null argument");
     const bool want_trace = trace != nullptr && trace_rows > 0;
-    if (want_trace && n_validate) {
-        if (!val_user || !val_item || !val_obs) return cf_set_error(ctx, CF_EINVAL, "cf_sgd_fit: null validation array");
-        for (uint64_t e = 0; e < n_validate; ++e)
-            if (val_user[e] >= n_users || val_item[e] >= n_items)
-                return cf_set_error(ctx, CF_EINVAL, "cf_sgd_fit: validation index out of range");
-    }
+    const uint64_t n_val = want_trace ? n_validate : 0;
+    CF_TRY(check_validation(ctx, "cf_sgd_fit", n_val, val_user, val_item, val_obs, n_users, n_items));
     if (n_users == 0) return CF_OK;   // nothing can be active
     CF_TRY(set_device(ctx));
     const bool bias = bias_user != nullptr;
-    const uint64_t n_val = want_trace ? n_validate : 0;
     if ((nnz + kAT - 1) / kAT > 0x7fffffffull || error_blocks(std::max(nnz, n_val)) > 0x7fffffffull)
         return cf_set_error(ctx, CF_ERANGE, "cf_sgd_fit: too many edges");
 
@@ -446,14 +249,8 @@ extern "C" int cf_sgd_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     const uint64_t seg_cap = std::max(total_segments(n_users, user_off), n_items ? total_segments(n_items, item_off) : 0);
     if (seg_cap > 0xffffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_sgd_fit: too many segments");
     SgdLayout f{};
-    {
-        Carver size;
-        carve_sgd(size, f, n_users, n_items, nnz, (int)D, bias, seg_cap, n_val, want_trace);
-        CF_TRY(als_reserve(ctx, size.pos));
-        Carver c;
-        c.base = static_cast<char*>(ctx->d_als);
-        carve_sgd(c, f, n_users, n_items, nnz, (int)D, bias, seg_cap, n_val, want_trace);
-    }
+    CF_TRY(carve_workspace(
+        ctx, [&](Carver& c) { carve_sgd(c, f, n_users, n_items, nnz, (int)D, bias, seg_cap, n_val, want_trace); }));
     MfEvents<8> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
     hipStream_t st = nullptr;
@@ -468,31 +265,15 @@ extern "C" int cf_sgd_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     for (int k = 0; k < 2; ++k) {
         if (n[k] == 0) continue;
         const SgdSide& s = f.side[k];
-        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.off, h_off[k], sizeof(uint64_t) * ((size_t)n[k] + 1), hipMemcpyHostToDevice));
-        if (nnz) {
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.nbr, h_nbr[k], sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.obs, h_obs[k], sizeof(float) * nnz, hipMemcpyHostToDevice));
-            std::vector<uint32_t> src(nnz);
-            for (uint32_t v = 0; v < n[k]; ++v)
-                for (uint64_t e = h_off[k][v]; e < h_off[k][v + 1]; ++e) src[e] = v;
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-        }
+        CF_TRY(upload_side(ctx, s, nnz, h_off[k], h_nbr[k], h_obs[k], h_nupd[k], k == 0 ? activate_user : nullptr, k == 0));
         CF_HIP_CHECK(ctx, hipMemcpy(s.F, h_F[k], sizeof(double) * (size_t)n[k] * D, hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemset(s.dF, 0, sizeof(double) * (size_t)n[k] * D));
         if (bias) {
             CF_HIP_CHECK(ctx, hipMemcpy(s.b, h_b[k], sizeof(double) * n[k], hipMemcpyHostToDevice));
             CF_HIP_CHECK(ctx, hipMemset(s.db, 0, sizeof(double) * n[k]));
         }
-        CF_HIP_CHECK(ctx, hipMemcpy(s.nupd, h_nupd[k], sizeof(uint32_t) * n[k], hipMemcpyHostToDevice));
-        if (k == 0 && activate_user) CF_HIP_CHECK(ctx, hipMemcpy(s.flag, activate_user, n[k], hipMemcpyHostToDevice));
-        else CF_HIP_CHECK(ctx, hipMemset(s.flag, k == 0 ? 1 : 0, n[k]));
-        CF_HIP_CHECK(ctx, hipMemset(s.active, 0, n[k]));
     }
-    if (n_val) {
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vuser, val_user, sizeof(uint32_t) * n_val, hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vitem, val_item, sizeof(uint32_t) * n_val, hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vobs, val_obs, sizeof(float) * n_val, hipMemcpyHostToDevice));
-    }
+    CF_TRY(upload_val(ctx, f.val, n_val, val_user, val_item, val_obs));
     CF_HIP_CHECK(ctx, hipMemset(f.counters, 0, 2 * sizeof(unsigned long long)));
 
     SgdArgs a{params->gamma, params->lambda, params->tol, params->minval, params->maxval, params->global_mean, (int)D};
@@ -542,7 +323,7 @@ extern "C" int cf_sgd_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
                 launch_error(st, nnz, su.src, su.nbr, su.obs, su.F, si.F, (int)D, su.b, si.b, a.mean, a.minval, a.maxval,
                              f.partial, f.sums);
             if (n_val)
-                launch_error(st, n_val, f.vuser, f.vitem, f.vobs, su.F, si.F, (int)D, su.b, si.b, a.mean, a.minval,
+                launch_error(st, n_val, f.val.user, f.val.item, f.val.obs, su.F, si.F, (int)D, su.b, si.b, a.mean, a.minval,
                              a.maxval, f.partial, f.sums + 1);
         }
         ++supersteps;

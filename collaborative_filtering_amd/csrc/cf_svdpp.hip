@@ -20,16 +20,15 @@
 // arrays and the copies in and out interleave them on the host.  The all-role list of a user is
 // its TRAIN items followed by its implicit items (one CSR built on the host).
 //
-// Work shape, lane mapping and the determinism rule are those of cf_sgd.hip:
-// eight edges per wave (lane group g = lane >> 3), lane sl of a group holds elements sl, sl + 8, ..
-// of each row in registers; low / mid / high classes with the cuts of cf_mf_common.h on the
-// vertex's own degree (all-role degree for P1, TRAIN degree for U2 and I2); wave partials are
-// summed in wave order, segment partials in segment order; no floating-point atomics.
+// The three reductions run on the shared skeleton of cf_mf_reduce.h (work shape, lane mapping,
+// every summation order: the determinism rule of DESIGN 3.12), with the classes taken on the
+// degree of the list that is walked (all-role degree for P1, TRAIN degree for U2 and I2); this
+// file supplies PpOp<kP1 | kU2 | kI2>.
 // Every kind reduces to D + 3 numbers per vertex: D sums, sum err, sum err c_u, count, with
 //   P1  s = sum Y_i
 //   U2  s = sum err V_i,            e = sum err                  (reg: user_factor_reg U_u e)
 //   I2  s = sum err (U_u + W_u),    e = sum err,  e2 = sum err c_u,  c_u = (float)(step2 usrNorm_u)
-// and the regularisers are applied in closed form by finish_*(), once per vertex.
+// and the regularisers are applied in closed form by PpOp::finish_*(), once per vertex.
 // edge_err() is one function called with (U row, V row, Y row) from both sides, so err_e has the
 // same float bits in U2 and I2.
 
@@ -37,11 +36,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <limits>
 #include <vector>
 
 #include "cf_internal.h"
-#include "cf_mf_common.h"
+#include "cf_mf_reduce.h"
 
 namespace {
 
@@ -89,15 +87,6 @@ struct PpArgs {
     int D;
 };
 
-template <int NJ>
-__device__ __forceinline__ void load_row(double (&x)[NJ], const double* __restrict__ row, int D, int sl) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int d = sl + kG * j;
-        x[j] = d < D ? row[d] : 0.0;
-    }
-}
-
 // err of one TRAIN edge from the register images of U_u, V_i and Y_i (svdpp.cpp:287-291).  A NaN
 // prediction stays NaN through the clamp, as std::min / std::max of the reference leave it.
 template <int NJ>
@@ -114,42 +103,45 @@ __device__ __forceinline__ float edge_err(const double (&u)[NJ], const double (&
     return (float)((double)obs - p);
 }
 
-template <int NJ>
-struct Acc {
-    double s[NJ];
-    double e, e2;
-    uint32_t cnt, nan;
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) s[j] = 0.0;
-        e = e2 = 0.0;
-        cnt = nan = 0;
+// The policy of one kind of reduction.  own.a / own.b: U_u (U2) or V_i, Y_i (I2); the sums x are
+// {sum err, sum err c_u}.
+template <int MODE>
+struct PpOp {
+    static constexpr int NS = 2;
+    static constexpr bool kCountNan = MODE == kU2;
+    PpGraph G;
+    PpArgs a;
+    template <int NJ>
+    struct Own {
+        double a[NJ], b[NJ];
+        double bias;
+    };
+    __host__ __device__ int dim() const { return a.D; }
+    // P1: the all-role list; U2, I2: the TRAIN list
+    __device__ __forceinline__ uint64_t begin(uint32_t v) const {
+        return MODE == kP1 ? G.all_off[v] : (MODE == kU2 ? G.u.off[v] : G.i.off[v]);
     }
-    // fixed butterfly over the eight groups: afterwards every lane holds the wave's sums
-    __device__ __forceinline__ void reduce_groups() {
+    __device__ __forceinline__ uint64_t end(uint32_t v) const {
+        return MODE == kP1 ? G.all_off[v + 1] : (MODE == kU2 ? G.u.off[v + 1] : G.i.off[v + 1]);
+    }
+    template <int NJ>
+    __device__ __forceinline__ void load_own(Own<NJ>& own, uint32_t v, int sl) const {
+        const int D = a.D;
 #pragma unroll
-        for (int o = kG; o < 64; o <<= 1) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) s[j] += __shfl_xor(s[j], o);
-            e += __shfl_xor(e, o);
-            e2 += __shfl_xor(e2, o);
-            cnt += __shfl_xor(cnt, o);
-            nan += __shfl_xor(nan, o);
+        for (int j = 0; j < NJ; ++j) own.a[j] = own.b[j] = 0.0;
+        own.bias = 0.0;
+        if (MODE == kU2) {
+            load_row<NJ>(own.a, G.u.F + (size_t)v * 2 * D, D, sl);
+            own.bias = G.u.b[v];
+        } else if (MODE == kI2) {
+            load_row<NJ>(own.a, G.i.F + (size_t)v * 2 * D, D, sl);
+            load_row<NJ>(own.b, G.i.F + (size_t)v * 2 * D + D, D, sl);
+            own.bias = G.i.b[v];
         }
     }
-};
-
-// acc += the edges [p0, p1) of vertex v's list (P1: all-role list; U2, I2: TRAIN list).  ownA /
-// ownB: U_u (U2) or V_i, Y_i (I2).  Called by a whole wave.
-template <int NJ, int MODE>
-__device__ __forceinline__ void wave_accumulate(Acc<NJ>& acc, const double (&ownA)[NJ], const double (&ownB)[NJ],
-                                                double own_bias, const PpGraph& G, const PpArgs& a, uint64_t p0,
-                                                uint64_t p1, int lane) {
-    const int g = lane >> 3, sl = lane & (kG - 1);
-    const int D = a.D;
-    for (uint64_t base = p0; base < p1; base += 64 / kG) {
-        const uint64_t e = base + g;
-        if (e >= p1) continue;   // whole groups
+    template <int NJ>
+    __device__ __forceinline__ void edge(Acc<NJ, NS>& acc, const Own<NJ>& own, uint64_t e, int sl) const {
+        const int D = a.D;
         if (MODE == kP1) {
             double y[NJ];
             load_row<NJ>(y, G.i.F + (size_t)G.all_item[e] * 2 * D + D, D, sl);
@@ -162,196 +154,65 @@ __device__ __forceinline__ void wave_accumulate(Acc<NJ>& acc, const double (&own
             double v[NJ], y[NJ];
             load_row<NJ>(v, row, D, sl);
             load_row<NJ>(y, row + D, D, sl);
-            const float err = edge_err<NJ>(ownA, v, y, a.mean, own_bias, G.i.b[w], G.u.obs[e], a.minval, a.maxval);
+            const float err = edge_err<NJ>(own.a, v, y, a.mean, own.bias, G.i.b[w], G.u.obs[e], a.minval, a.maxval);
             if (err != err) acc.nan += sl == 0;
             const double ed = (double)err;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc.s[j] = fma(ed, v[j], acc.s[j]);
-            acc.e += ed;
+            acc.x[0] += ed;
             acc.cnt += 1;
         } else {
             const uint32_t w = G.i.nbr[e];
-            if (!G.act2[w]) continue;   // the user did not run phase 2: no message on this edge
+            if (!G.act2[w]) return;   // the user did not run phase 2: no message on this edge
             const double* row = G.u.F + (size_t)w * 2 * D;
             double uu[NJ], ww[NJ];
             load_row<NJ>(uu, row, D, sl);
             load_row<NJ>(ww, row + D, D, sl);
-            const float err = edge_err<NJ>(uu, ownA, ownB, a.mean, G.u.b[w], own_bias, G.i.obs[e], a.minval, a.maxval);
+            const float err = edge_err<NJ>(uu, own.a, own.b, a.mean, G.u.b[w], own.bias, G.i.obs[e], a.minval, a.maxval);
             const double ed = (double)err;
             const float c = a.if2s * G.unorm[w];   // float product (svdpp.cpp:307-308)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc.s[j] = fma(ed, uu[j] + ww[j], acc.s[j]);
-            acc.e += ed;
-            acc.e2 = fma(ed, (double)c, acc.e2);
+            acc.x[0] += ed;
+            acc.x[1] = fma(ed, (double)c, acc.x[1]);
             acc.cnt += 1;
         }
     }
-}
-
-template <int MODE>
-__device__ __forceinline__ uint64_t list_begin(const PpGraph& G, uint32_t v) {
-    return MODE == kP1 ? G.all_off[v] : (MODE == kU2 ? G.u.off[v] : G.i.off[v]);
-}
-template <int MODE>
-__device__ __forceinline__ uint64_t list_end(const PpGraph& G, uint32_t v) {
-    return MODE == kP1 ? G.all_off[v + 1] : (MODE == kU2 ? G.u.off[v + 1] : G.i.off[v + 1]);
-}
-
-// Element d of vertex v's pending values from its sums; the regularisers in closed form.
-template <int MODE>
-__device__ __forceinline__ void finish_elem(const PpGraph& G, const PpArgs& a, uint32_t v, int d, double sum, double e,
-                                            double e2, double cnt) {
-    const int D = a.D;
-    const size_t at = (size_t)v * 2 * D + d;
-    if (MODE == kP1) {
-        G.u.dF[at + D] = cnt > 0.0 ? sum * (double)G.unorm[v] : G.u.F[at + D];
-    } else if (MODE == kU2) {
-        G.u.dF[at] = (double)a.ufs * (sum - (double)a.ufr * G.u.F[at] * e);
-    } else {
-        const double own_v = G.i.F[at], own_y = G.i.F[at + D];
-        const float mult = a.if2s * a.if2r;   // float product, then double (svdpp.cpp:310)
-        G.i.dF[at] = (double)a.ifs * (sum - cnt * (double)a.ifr * own_v);
-        G.i.dF[at + D] = own_v * e2 - cnt * (double)mult * own_y;
-    }
-}
-
-// counters: [0] NaN errors, [1] messages (edges the item reduction accepted)
-template <int MODE>
-__device__ __forceinline__ void finish_scalar(const PpGraph& G, const PpArgs& a, uint32_t v, double e, double cnt,
-                                              unsigned long long* counters) {
-    if (MODE == kU2) G.u.db[v] = (double)a.ubs * e;
-    if (MODE == kI2) {
-        G.i.db[v] = (double)a.ibs * e;
-        if (cnt > 0.0) atomicAdd(&counters[1], (unsigned long long)cnt);
-    }
-}
-
-template <int NJ, int MODE>
-__device__ __forceinline__ void load_own(double (&ownA)[NJ], double (&ownB)[NJ], double& own_bias, const PpGraph& G,
-                                         uint32_t v, int D, int sl) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) ownA[j] = ownB[j] = 0.0;
-    own_bias = 0.0;
-    if (MODE == kU2) {
-        load_row<NJ>(ownA, G.u.F + (size_t)v * 2 * D, D, sl);
-        own_bias = G.u.b[v];
-    } else if (MODE == kI2) {
-        load_row<NJ>(ownA, G.i.F + (size_t)v * 2 * D, D, sl);
-        load_row<NJ>(ownB, G.i.F + (size_t)v * 2 * D + D, D, sl);
-        own_bias = G.i.b[v];
-    }
-}
-
-// low class: one wave per vertex.
-template <int NJ, int MODE>
-__global__ __launch_bounds__(kAT) void svdpp_low_kernel(PpGraph G, PpArgs a, const uint32_t* __restrict__ list,
-                                                       uint32_t count_v, unsigned long long* counters) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count_v) return;   // whole waves leave; no block barrier below
-    const uint32_t v = list[j];
-    const int sl = lane & (kG - 1);
-    double ownA[NJ], ownB[NJ], own_bias;
-    load_own<NJ, MODE>(ownA, ownB, own_bias, G, v, a.D, sl);
-    Acc<NJ> acc;
-    acc.clear();
-    wave_accumulate<NJ, MODE>(acc, ownA, ownB, own_bias, G, a, list_begin<MODE>(G, v), list_end<MODE>(G, v), lane);
-    acc.reduce_groups();
-    if (lane < kG) {
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int d = sl + kG * jj;
-            if (d < a.D) finish_elem<MODE>(G, a, v, d, acc.s[jj], acc.e, acc.e2, (double)acc.cnt);
+    // Element d of vertex v's pending values from its sums; the regularisers in closed form.
+    __device__ __forceinline__ void finish_elem(uint32_t v, int d, double sum, const double* x, double cnt) const {
+        const int D = a.D;
+        const size_t at = (size_t)v * 2 * D + d;
+        if (MODE == kP1) {
+            G.u.dF[at + D] = cnt > 0.0 ? sum * (double)G.unorm[v] : G.u.F[at + D];
+        } else if (MODE == kU2) {
+            G.u.dF[at] = (double)a.ufs * (sum - (double)a.ufr * G.u.F[at] * x[0]);
+        } else {
+            const double own_v = G.i.F[at], own_y = G.i.F[at + D];
+            const float mult = a.if2s * a.if2r;   // float product, then double (svdpp.cpp:310)
+            G.i.dF[at] = (double)a.ifs * (sum - cnt * (double)a.ifr * own_v);
+            G.i.dF[at + D] = own_v * x[1] - cnt * (double)mult * own_y;
         }
     }
-    if (lane == 0) {
-        finish_scalar<MODE>(G, a, v, acc.e, (double)acc.cnt, counters);
-        if (MODE == kU2 && acc.nan) atomicAdd(&counters[0], (unsigned long long)acc.nan);
-    }
-}
-
-constexpr int kPpSlotMax = CF_ALS_MAX_D + 3;   // D sums, sum err, sum err c, the count
-
-// mid class (SEGMENT = false): one workgroup per vertex.  high class (SEGMENT = true): one
-// workgroup per (vertex, segment); its D + 3 partial sums go to workspace slot blockIdx.x.
-template <int NJ, int MODE, bool SEGMENT>
-__global__ __launch_bounds__(kAT) void svdpp_group_kernel(PpGraph G, PpArgs a, const uint32_t* __restrict__ list,
-                                                         const uint32_t* __restrict__ seg_index, double* ws,
-                                                         unsigned long long* counters) {
-    __shared__ double part[kWaves][kPpSlotMax];
-    __shared__ double tot[kPpSlotMax];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sl = lane & (kG - 1);
-    const int D = a.D;
-    const uint32_t v = list[blockIdx.x];
-    uint64_t p0 = list_begin<MODE>(G, v);
-    uint64_t len = list_end<MODE>(G, v) - p0;
-    if (SEGMENT) {
-        const uint64_t first = (uint64_t)seg_index[blockIdx.x] * kSeg;
-        p0 += first;
-        len = len - first < (uint64_t)kSeg ? len - first : (uint64_t)kSeg;
-    }
-    const uint64_t chunk = (len + kWaves - 1) / kWaves;
-    const uint64_t b = std::min(len, wave * chunk), e = std::min(len, (wave + 1) * chunk);
-    double ownA[NJ], ownB[NJ], own_bias;
-    load_own<NJ, MODE>(ownA, ownB, own_bias, G, v, D, sl);
-    Acc<NJ> acc;
-    acc.clear();
-    wave_accumulate<NJ, MODE>(acc, ownA, ownB, own_bias, G, a, p0 + b, p0 + e, lane);
-    acc.reduce_groups();
-    if (lane < kG) {
-#pragma unroll
-        for (int jj = 0; jj < NJ; ++jj) {
-            const int d = sl + kG * jj;
-            if (d < D) part[wave][d] = acc.s[jj];
+    // counters[1]: messages (edges the item reduction accepted)
+    __device__ __forceinline__ void finish_scalar(uint32_t v, const double* x, double cnt,
+                                                  unsigned long long* counters) const {
+        if (MODE == kU2) G.u.db[v] = (double)a.ubs * x[0];
+        if (MODE == kI2) {
+            G.i.db[v] = (double)a.ibs * x[0];
+            if (cnt > 0.0) atomicAdd(&counters[1], (unsigned long long)cnt);
         }
     }
-    if (lane == 0) {
-        part[wave][D] = acc.e;
-        part[wave][D + 1] = acc.e2;
-        part[wave][D + 2] = (double)acc.cnt;
-        if (MODE == kU2 && acc.nan) atomicAdd(&counters[0], (unsigned long long)acc.nan);
+    template <int NJ>
+    __device__ __forceinline__ void finish_elem_own(const Own<NJ>&, int, uint32_t v, int d, double sum, const double* x,
+                                                    double cnt) const {
+        finish_elem(v, d, sum, x, cnt);
     }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < D + 3) {   // partials summed in wave order
-        double sum = part[0][t];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) sum += part[w][t];
-        if (SEGMENT) ws[(size_t)blockIdx.x * (D + 3) + t] = sum;
-        else tot[t] = sum;
+    template <int NJ>
+    __device__ __forceinline__ void finish_scalar_own(const Own<NJ>&, uint32_t v, const double* x, double cnt,
+                                                      unsigned long long* counters) const {
+        finish_scalar(v, x, cnt, counters);
     }
-    if (SEGMENT) return;
-    __syncthreads();
-    if (t < D) finish_elem<MODE>(G, a, v, t, tot[t], tot[D], tot[D + 1], tot[D + 2]);
-    if (t == 0) finish_scalar<MODE>(G, a, v, tot[D], tot[D + 2], counters);
-}
-
-// high class, second pass: one wave per vertex adds its segments' partials in segment order.
-template <int MODE>
-__global__ __launch_bounds__(kAT) void svdpp_finish_kernel(PpGraph G, PpArgs a, const uint32_t* __restrict__ list,
-                                                          const uint32_t* __restrict__ base, uint32_t count_v,
-                                                          const double* __restrict__ ws, unsigned long long* counters) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count_v) return;
-    const uint32_t v = list[j];
-    const int D = a.D, n = D + 3;
-    const uint64_t deg = list_end<MODE>(G, v) - list_begin<MODE>(G, v);
-    const uint32_t nseg = (uint32_t)((deg + kSeg - 1) / kSeg);
-    const double* slot = ws + (size_t)base[j] * n;
-    double esum = slot[D], e2sum = slot[D + 1], cnt = slot[D + 2];   // every lane adds these itself, in the same order
-    for (uint32_t q = 1; q < nseg; ++q) {
-        esum += slot[(size_t)q * n + D];
-        e2sum += slot[(size_t)q * n + D + 1];
-        cnt += slot[(size_t)q * n + D + 2];
-    }
-    for (int d = lane; d < D; d += 64) {
-        double sum = slot[d];
-        for (uint32_t q = 1; q < nseg; ++q) sum += slot[(size_t)q * n + d];
-        finish_elem<MODE>(G, a, v, d, sum, esum, e2sum, cnt);
-    }
-    if (lane == 0) finish_scalar<MODE>(G, a, v, esum, cnt, counters);
-}
+};
 
 // The flags of one side split by the vertex's own phase.  Users: f1 = phase 1, f2 = phase 2.
 // Items: f1 = every signalled item (it counts an update and signals its users), f2 = those in
@@ -406,20 +267,6 @@ __global__ __launch_bounds__(kAT) void svdpp_commit_item_kernel(PpGraph G, int D
     if (d == 0) G.i.nupd[v] += 1;
 }
 
-// scatter (svdpp.cpp:388-397) over the TRAIN edges of one side: an edge whose owner is marked in
-// `on` signals its other end while that has updates left.  max_updates = UINT64_MAX with every
-// edge of any role is the uncapped signalling of the phase-1 users (svdpp.cpp:282).
-__global__ __launch_bounds__(kAT) void svdpp_signal_kernel(const uint32_t* __restrict__ src, const uint32_t* __restrict__ nbr,
-                                                          uint64_t nnz, const uint8_t* __restrict__ on,
-                                                          const uint32_t* __restrict__ nupd_o, uint8_t* flag_o,
-                                                          uint64_t max_updates, bool capped) {
-    const uint64_t e = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (e >= nnz) return;
-    if (!on[src[e]]) return;
-    const uint32_t w = nbr[e];
-    if (!capped || (uint64_t)nupd_o[w] < max_updates) flag_o[w] = 1;
-}
-
 // The first D of every 2 D-long row (U or V alone) for the error reduction of the trace.
 __global__ __launch_bounds__(kAT) void svdpp_front_kernel(const double* __restrict__ F, uint64_t total, int D, double* out) {
     const uint64_t idx = (uint64_t)blockIdx.x * kAT + threadIdx.x;
@@ -439,9 +286,7 @@ struct PpLayout {
     uint8_t* iflag_all;
     double* ws;
     unsigned long long* counters;
-    uint32_t* vuser;
-    uint32_t* vitem;
-    float* vobs;
+    MfVal val;
     double* Uf;          // n_users x D and n_items x D fronts for the trace
     double* Vf;
     double* partial;
@@ -455,18 +300,11 @@ void carve_svdpp(Carver& c, PpLayout& f, uint32_t n_users, uint32_t n_items, uin
     PpSide* side[2] = {&f.G.u, &f.G.i};
     for (int k = 0; k < 2; ++k) {
         PpSide& s = *side[k];
-        s.n = n[k];
-        s.off = c.take<uint64_t>((size_t)n[k] + 1);
-        s.nbr = c.take<uint32_t>(nnz);
-        s.obs = c.take<float>(nnz);
-        s.src = c.take<uint32_t>(nnz);
+        carve_side(c, s, n[k], nnz);
         s.F = c.take<double>((size_t)n[k] * 2 * D);
         s.dF = c.take<double>((size_t)n[k] * 2 * D);
         s.b = c.take<double>(n[k]);
         s.db = c.take<double>(n[k]);
-        s.nupd = c.take<uint32_t>(n[k]);
-        s.flag = c.take<uint8_t>(n[k]);
-        s.active = c.take<uint8_t>(n[k]);
     }
     f.G.all_off = c.take<uint64_t>((size_t)n_users + 1);
     f.G.all_item = c.take<uint32_t>(n_all);
@@ -484,11 +322,9 @@ void carve_svdpp(Carver& c, PpLayout& f, uint32_t n_users, uint32_t n_items, uin
     f.view[2] = PpView{n_items, f.G.i.off, f.iflag_all, f.G.i.active};
     f.view[3] = PpView{n_items, f.G.i.off, f.iflag2, f.G.iact2};
     for (int q = 0; q < 4; ++q) carve_lists(c, f.lists[q], q < 2 ? n_users : n_items, seg_cap);
-    f.ws = c.take<double>((size_t)seg_cap * (D + 3));
+    f.ws = c.take<double>((size_t)seg_cap * (D + 3));   // D sums, sum err, sum err c, the count
     f.counters = c.take<unsigned long long>(2);
-    f.vuser = c.take<uint32_t>(trace ? n_val : 0);
-    f.vitem = c.take<uint32_t>(trace ? n_val : 0);
-    f.vobs = c.take<float>(trace ? n_val : 0);
+    carve_val(c, f.val, n_val);
     f.Uf = c.take<double>(trace ? (size_t)n_users * D : 0);
     f.Vf = c.take<double>(trace ? (size_t)n_items * D : 0);
     f.partial = c.take<double>(trace ? error_blocks(std::max(nnz, n_val)) : 0);
@@ -496,34 +332,10 @@ void carve_svdpp(Carver& c, PpLayout& f, uint32_t n_users, uint32_t n_items, uin
     f.seg_cap = (uint32_t)seg_cap;
 }
 
-template <int NJ, int MODE>
-void launch_reduce_t(const PpLayout& f, const PpArgs& a, const uint32_t rec[4], hipStream_t st) {
-    const AlsLists& L = f.lists[MODE == kP1 ? 0 : (MODE == kU2 ? 1 : 3)];
-    if (rec[0])
-        hipLaunchKernelGGL((svdpp_low_kernel<NJ, MODE>), dim3((rec[0] + kWaves - 1) / kWaves), dim3(kAT), 0, st, f.G, a,
-                           (const uint32_t*)L.low, rec[0], f.counters);
-    if (rec[1])
-        hipLaunchKernelGGL((svdpp_group_kernel<NJ, MODE, false>), dim3(rec[1]), dim3(kAT), 0, st, f.G, a,
-                           (const uint32_t*)L.mid, (const uint32_t*)nullptr, (double*)nullptr, f.counters);
-    if (rec[2]) {
-        hipLaunchKernelGGL((svdpp_group_kernel<NJ, MODE, true>), dim3(rec[3]), dim3(kAT), 0, st, f.G, a,
-                           (const uint32_t*)L.seg_vertex, (const uint32_t*)L.seg_index, f.ws, f.counters);
-        hipLaunchKernelGGL(svdpp_finish_kernel<MODE>, dim3((rec[2] + kWaves - 1) / kWaves), dim3(kAT), 0, st, f.G, a,
-                           (const uint32_t*)L.high, (const uint32_t*)L.high_base, rec[2], (const double*)f.ws, f.counters);
-    }
-}
-
 template <int MODE>
 void launch_reduce(const PpLayout& f, const PpArgs& a, const uint32_t rec[4], hipStream_t st) {
-    const int D = a.D;
-    if (D <= 8) launch_reduce_t<1, MODE>(f, a, rec, st);
-    else if (D <= 16) launch_reduce_t<2, MODE>(f, a, rec, st);
-    else if (D <= 24) launch_reduce_t<3, MODE>(f, a, rec, st);
-    else if (D <= 32) launch_reduce_t<4, MODE>(f, a, rec, st);
-    else launch_reduce_t<8, MODE>(f, a, rec, st);
+    launch_reduce(PpOp<MODE>{f.G, a}, f.lists[MODE == kP1 ? 0 : (MODE == kU2 ? 1 : 3)], rec, f.ws, f.counters, st);
 }
-
-unsigned blocks_for(uint64_t n) { return (unsigned)((n + kAT - 1) / kAT); }
 
 // the master flags of one side -> its two views' flags -> their class lists
 void launch_split_compact(const PpLayout& f, bool item, uint64_t max_updates, hipStream_t st) {
@@ -539,12 +351,6 @@ void launch_split_compact(const PpLayout& f, bool item, uint64_t max_updates, hi
     }
     launch_compact(f.view[q], f.lists[q], st);
     launch_compact(f.view[q + 1], f.lists[q + 1], st);
-}
-
-float elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
 }
 
 uint64_t sum3(const uint32_t rec[4]) { return (uint64_t)rec[0] + rec[1] + rec[2]; }
@@ -577,9 +383,7 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
     uint64_t nnz = 0;
     CF_TRY(check_two_csr(ctx, "cf_svdpp_fit", n_users, n_items, D, user_off, user_item, user_obs, item_off, item_user,
                          item_obs, &nnz));
-    if (params->max_updates == std::numeric_limits<uint64_t>::max() && params->max_supersteps == 0)
-        return cf_set_error(ctx, CF_EINVAL,
-                            "cf_svdpp_fit: neither max_updates nor max_supersteps is set (the run would never end)");
+    CF_TRY(check_caps(ctx, "cf_svdpp_fit", params->max_updates, params->max_supersteps));
     if ((n_users && (!U || !W || !bias_user || !nupdates_user)) || (n_items && (!V || !Y || !bias_item || !nupdates_item)))
         return cf_set_error(ctx, CF_EINVAL, "cf_svdpp_fit: null argument");
     uint64_t n_imp = 0;
@@ -589,15 +393,10 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
         CF_TRY(check_csr(ctx, "cf_svdpp_fit", "implicit", n_users, imp_off, imp_item, n_items));
     }
     const bool want_trace = trace != nullptr && trace_rows > 0;
-    if (want_trace && n_validate) {
-        if (!val_user || !val_item || !val_obs) return cf_set_error(ctx, CF_EINVAL, "cf_svdpp_fit: null validation array");
-        for (uint64_t e = 0; e < n_validate; ++e)
-            if (val_user[e] >= n_users || val_item[e] >= n_items)
-                return cf_set_error(ctx, CF_EINVAL, "cf_svdpp_fit: validation index out of range");
-    }
+    const uint64_t n_val = want_trace ? n_validate : 0;
+    CF_TRY(check_validation(ctx, "cf_svdpp_fit", n_val, val_user, val_item, val_obs, n_users, n_items));
     if (n_users == 0) return CF_OK;   // nothing can be active
     CF_TRY(set_device(ctx));
-    const uint64_t n_val = want_trace ? n_validate : 0;
     const uint64_t n_all = nnz + n_imp;
     if ((n_all + kAT - 1) / kAT > 0x7fffffffull || error_blocks(std::max(nnz, n_val)) > 0x7fffffffull ||
         (uint64_t)std::max(n_users, n_items) * D > 0x7fffffffull * (uint64_t)kAT)
@@ -623,14 +422,8 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
                                        n_items ? total_segments(n_items, item_off) : (uint64_t)0});
     if (seg_cap > 0xffffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_svdpp_fit: too many segments");
     PpLayout f{};
-    {
-        Carver size;
-        carve_svdpp(size, f, n_users, n_items, nnz, n_all, (int)D, seg_cap, n_val, want_trace);
-        CF_TRY(als_reserve(ctx, size.pos));
-        Carver c;
-        c.base = static_cast<char*>(ctx->d_als);
-        carve_svdpp(c, f, n_users, n_items, nnz, n_all, (int)D, seg_cap, n_val, want_trace);
-    }
+    CF_TRY(carve_workspace(
+        ctx, [&](Carver& c) { carve_svdpp(c, f, n_users, n_items, nnz, n_all, (int)D, seg_cap, n_val, want_trace); }));
     MfEvents<9> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
     hipStream_t st = nullptr;
@@ -649,15 +442,7 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
     for (int k = 0; k < 2; ++k) {
         if (n[k] == 0) continue;
         const PpSide& s = *side[k];
-        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.off, h_off[k], sizeof(uint64_t) * ((size_t)n[k] + 1), hipMemcpyHostToDevice));
-        if (nnz) {
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.nbr, h_nbr[k], sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.obs, h_obs[k], sizeof(float) * nnz, hipMemcpyHostToDevice));
-            std::vector<uint32_t> src(nnz);
-            for (uint32_t v = 0; v < n[k]; ++v)
-                for (uint64_t e = h_off[k][v]; e < h_off[k][v + 1]; ++e) src[e] = v;
-            CF_HIP_CHECK(ctx, hipMemcpy((void*)s.src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-        }
+        CF_TRY(upload_side(ctx, s, nnz, h_off[k], h_nbr[k], h_obs[k], h_nupd[k], k == 0 ? activate_user : nullptr, k == 0));
         rows.resize((size_t)n[k] * 2 * D);   // interleave [A | B]
         for (uint32_t v = 0; v < n[k]; ++v)
             for (uint32_t d = 0; d < D; ++d) {
@@ -668,10 +453,6 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
         CF_HIP_CHECK(ctx, hipMemset(s.dF, 0, sizeof(double) * rows.size()));
         CF_HIP_CHECK(ctx, hipMemcpy(s.b, h_b[k], sizeof(double) * n[k], hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemset(s.db, 0, sizeof(double) * n[k]));
-        CF_HIP_CHECK(ctx, hipMemcpy(s.nupd, h_nupd[k], sizeof(uint32_t) * n[k], hipMemcpyHostToDevice));
-        if (k == 0 && activate_user) CF_HIP_CHECK(ctx, hipMemcpy(s.flag, activate_user, n[k], hipMemcpyHostToDevice));
-        else CF_HIP_CHECK(ctx, hipMemset(s.flag, k == 0 ? 1 : 0, n[k]));
-        CF_HIP_CHECK(ctx, hipMemset(s.active, 0, n[k]));
     }
     CF_HIP_CHECK(ctx, hipMemcpy((void*)G.all_off, all_off.data(), sizeof(uint64_t) * all_off.size(), hipMemcpyHostToDevice));
     if (n_all) {
@@ -682,11 +463,7 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
     CF_HIP_CHECK(ctx, hipMemset(G.act1, 0, n_users));
     CF_HIP_CHECK(ctx, hipMemset(G.act2, 0, n_users));
     if (n_items) CF_HIP_CHECK(ctx, hipMemset(G.iact2, 0, n_items));
-    if (n_val) {
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vuser, val_user, sizeof(uint32_t) * n_val, hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vitem, val_item, sizeof(uint32_t) * n_val, hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(f.vobs, val_obs, sizeof(float) * n_val, hipMemcpyHostToDevice));
-    }
+    CF_TRY(upload_val(ctx, f.val, n_val, val_user, val_item, val_obs));
     CF_HIP_CHECK(ctx, hipMemset(f.counters, 0, 2 * sizeof(unsigned long long)));
 
     const uint64_t max_updates = params->max_updates;
@@ -718,10 +495,10 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
         if (n_items) {
             if (nnz && sum3(rec_u2))   // the scatter of the phase-2 users (a phase-1 user's is contained in the next)
-                hipLaunchKernelGGL(svdpp_signal_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, G.u.src, G.u.nbr, nnz,
+                hipLaunchKernelGGL(mf_signal_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, G.u.src, G.u.nbr, nnz,
                                    (const uint8_t*)G.act2, (const uint32_t*)G.i.nupd, G.i.flag, max_updates, true);
             if (n_all && sum3(rec_u1))
-                hipLaunchKernelGGL(svdpp_signal_kernel, dim3(blocks_for(n_all)), dim3(kAT), 0, st, G.all_src, G.all_item,
+                hipLaunchKernelGGL(mf_signal_kernel, dim3(blocks_for(n_all)), dim3(kAT), 0, st, G.all_src, G.all_item,
                                    n_all, (const uint8_t*)G.act1, (const uint32_t*)G.i.nupd, G.i.flag, max_updates, false);
         }
         launch_split_compact(f, true, max_updates, st);
@@ -754,7 +531,7 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
                 launch_error(st, nnz, G.u.src, G.u.nbr, G.u.obs, f.Uf, f.Vf, (int)D, G.u.b, G.i.b, a.mean, a.minval,
                              a.maxval, f.partial, f.sums);
             if (n_val)
-                launch_error(st, n_val, f.vuser, f.vitem, f.vobs, f.Uf, f.Vf, (int)D, G.u.b, G.i.b, a.mean, a.minval,
+                launch_error(st, n_val, f.val.user, f.val.item, f.val.obs, f.Uf, f.Vf, (int)D, G.u.b, G.i.b, a.mean, a.minval,
                              a.maxval, f.partial, f.sums + 1);
         }
         ++supersteps;
@@ -774,7 +551,7 @@ extern "C" int cf_svdpp_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uin
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[7], st));
         hipLaunchKernelGGL(svdpp_commit_item_kernel, dim3(blocks_for((uint64_t)n_items * D)), dim3(kAT), 0, st, G, (int)D);
         if (nnz)
-            hipLaunchKernelGGL(svdpp_signal_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, G.i.src, G.i.nbr, nnz,
+            hipLaunchKernelGGL(mf_signal_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, G.i.src, G.i.nbr, nnz,
                                (const uint8_t*)G.i.active, (const uint32_t*)G.u.nupd, G.u.flag, max_updates, true);
         launch_split_compact(f, false, max_updates, st);
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[8], st));

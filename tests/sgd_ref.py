@@ -156,6 +156,11 @@ CASES = {
     "B": (96, 40, 33, 0, 4),
     "C": (200, 12, 4, 60, 5),
     "E": (96, 40, 64, 0, 4),
+    # the shape of "C" (items on the workgroup path) in the two D tiers the others leave out:
+    # 9..16 (two row elements per lane) and 25..32 (four).  13, not 12: at D = 12 none of the 50
+    # pairs that the GPU prediction tests draw is clamped with biases, which they require
+    "F": (200, 12, 13, 60, 3),
+    "G": (200, 12, 28, 60, 3),
 }
 HYPER = dict(lam=0.05, gamma=0.02, step_dec=0.9, tol=0.5, minval=1.0, maxval=5.0)
 KEYS = [(name, bias) for name in CASES for bias in (False, True)]

@@ -186,8 +186,8 @@ def fit(user, item, obs, n_users, n_items, U0, V0, W0, Y0, *, implicit=None, ste
 
 # ---- the cases the CPU and GPU tests share ------------------------------------------------
 
-NAMES = ["A", "B", "C", "E"]
-MAX_UPDATES = {"A": 6, "B": 4, "C": 4, "E": 4}   # phase-1 and phase-2 updates alike: 3 / 2 gradient passes
+NAMES = ["A", "B", "C", "E", "F", "G"]
+MAX_UPDATES = {"A": 6, "B": 4, "C": 4, "E": 4, "F": 4, "G": 4}# phase-1 and phase-2 updates alike: 3 / 2 gradient passes
 
 
 @dataclass

@@ -170,13 +170,13 @@ def test_independent_of_the_active_set(gpu_ctx, bias):
     assert np.array_equal(got.nupdates_user, ref.nupdates_user) and np.array_equal(got.nupdates_item, ref.nupdates_item)
 
 
+@pytest.mark.parametrize("D", [4, 28])
 @pytest.mark.parametrize("bias", [False, True])
-def test_segmented_vertex(gpu_ctx, bias):
+def test_segmented_vertex(gpu_ctx, bias, D):
     """Item 0 is rated by segment + 52 users (two segment partials in HBM), item 1 and user 0 are
     above the low cut (one workgroup each), everything else takes one wave."""
     lib = _native.load()
     user, item, obs, nu, ni = sr.segmented_problem(lib.cf_debug_als_segment(), lib.cf_debug_als_low_max())
-    D = 4
     rng = np.random.default_rng(6)
     U0, V0 = rng.uniform(-1, 1, (nu, D)), rng.uniform(-1, 1, (ni, D))
     hyper = dict(sr.HYPER, gamma=0.002)

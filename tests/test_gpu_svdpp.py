@@ -151,13 +151,14 @@ def test_independent_of_the_active_set(gpu_ctx):
     assert got.messages == ref.messages and got.updates == ref.updates
 
 
-def test_segmented_vertex(gpu_ctx):
+@pytest.mark.parametrize("D", [4, 28])
+def test_segmented_vertex(gpu_ctx, D):
     """Item 0 is rated by segment + 52 users (two segment partials in HBM), item 1 and user 0 are
     above the low cut on the TRAIN list (one workgroup each), user 1 is above it on its all-role
     list only (phase 1 takes the workgroup path, phase 2 one wave), everything else takes one wave."""
     lib = _native.load()
     user, item, obs, nu, ni, iu, ii, (U0, V0, W0, Y0) = pr.segmented_case(lib.cf_debug_als_segment(),
-                                                                          lib.cf_debug_als_low_max())
+                                                                          lib.cf_debug_als_low_max(), D)
     low = lib.cf_debug_als_low_max()
     du = np.bincount(user, minlength=nu)
     assert du[1] <= low < du[1] + np.sum(iu == 1)
