@@ -152,6 +152,10 @@ SIGNATURES = {
     "cf_set_topn_block": (c_int, [c_void_p, c_uint32]),
     "cf_debug_topn_tile_users": (c_int, []),
     "cf_debug_topn_tile_items": (c_int, []),
+    "cf_ials_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 10 + [c_uint32] + [c_void_p] * 4),
+    "cf_ials_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 13),
+    "cf_mf_gram": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "cf_debug_ials_gram_rows": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }
@@ -174,6 +178,12 @@ class AlsStats(ctypes.Structure):
     """cf_als_stats (cf_abi.h)."""
     _fields_ = [("supersteps", c_uint32), ("updates", c_uint64), ("n_not_pd", c_uint64),
                 ("update_ms", c_float), ("scatter_ms", c_float)]
+
+
+class IalsStats(ctypes.Structure):
+    """cf_ials_stats (cf_abi.h)."""
+    _fields_ = [("sweeps", c_uint32), ("n_not_pd", c_uint64), ("gram_ms", c_float), ("update_ms", c_float),
+                ("loss_ms", c_float)]
 
 
 class SgdParams(ctypes.Structure):

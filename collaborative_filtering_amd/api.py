@@ -79,6 +79,21 @@ class AlsResult:
 
 
 @dataclass
+class IalsResult:
+    """Outcome of Context.ials_fit: fitted factors, the loss after each half-sweep (2 * n_sweeps
+    values) and the cf_ials_stats of the run."""
+
+    U: np.ndarray
+    V: np.ndarray
+    loss_trace: np.ndarray
+    sweeps: int
+    n_not_pd: int
+    gram_ms: float
+    update_ms: float
+    loss_ms: float
+
+
+@dataclass
 class SgdResult:
     """Outcome of Context.sgd_fit: fitted factors and biases (None for plain SGD), per-vertex
     update counts, the trace (one row {sum sq err TRAIN, sum sq err VALIDATE} per user
@@ -674,6 +689,60 @@ class Context:
         self._chk(self.lib.cf_als_predict(self.h, len(user), ptr(user), ptr(item), U.shape[0], V.shape[0], U.shape[1],
                                           ptr(U), ptr(V), ptr(pred)), "cf_als_predict")
         return pred
+
+    # -- implicit-feedback ALS (Hu, Koren, Volinsky 2008) -----------------------------------
+    def _ials_graph(self, user, item, conf, pref, n_users, n_items, lam, reg_user, reg_item):
+        """The two CSRs (confidence and preference per edge) and the reg arrays as cf_ials_* take
+        them: (uoff, uitem, uconf, upref, ioff, iuser, iconf, ipref, ru, ri); pref None = NULLs."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        conf = np.ascontiguousarray(conf, dtype=np.float32)
+        uoff, uitem, uconf, ioff, iuser, iconf = _mf_csr_pair(user, item, conf, n_users, n_items)
+        upref = ipref = None
+        if pref is not None:
+            pref = np.ascontiguousarray(pref, dtype=np.float32)
+            upref, ipref = _csr(user, item, pref, n_users)[2], _csr(item, user, pref, n_items)[2]
+        ru = np.full(n_users, float(lam)) if reg_user is None else np.ascontiguousarray(reg_user, dtype=np.float64)
+        ri = np.full(n_items, float(lam)) if reg_item is None else np.ascontiguousarray(reg_item, dtype=np.float64)
+        if len(ru) != n_users or len(ri) != n_items:
+            raise ValueError("reg_user / reg_item do not hold one value per vertex")
+        return uoff, uitem, uconf, upref, ioff, iuser, iconf, ipref, ru, ri
+
+    def ials_fit(self, user, item, conf, n_users, n_items, U0, V0, *, pref=None, lam=0.1, reg_user=None,
+                 reg_item=None, n_sweeps=10, trace=True) -> "IalsResult":
+        """cf_ials_fit: n_sweeps sweeps of implicit-feedback ALS over the edges (user[e], item[e])
+        with confidence conf[e] >= 1 and preference pref[e] (None: all ones); every other pair of
+        the grid is preference 0 with confidence 1.  Regularisation per vertex: reg_user /
+        reg_item, or lam everywhere.  trace=False skips the loss evaluations."""
+        n_users, n_items, n_sweeps = int(n_users), int(n_items), int(n_sweeps)
+        (U, V), D = _mf_factors((U0, V0), (n_users, n_items), "U0 and V0", "U0 / V0")
+        g = self._ials_graph(user, item, conf, pref, n_users, n_items, lam, reg_user, reg_item)
+        loss = np.zeros(2 * n_sweeps, dtype=np.float64) if trace else None
+        st = _native.IalsStats()
+        self._chk(self.lib.cf_ials_fit(self.h, n_users, n_items, int(D), *[ptr(x) for x in g], n_sweeps, ptr(U), ptr(V),
+                                       ptr(loss), byref(st)), "cf_ials_fit")
+        return IalsResult(U, V, loss if trace else np.zeros(0), int(st.sweeps), int(st.n_not_pd), float(st.gram_ms),
+                          float(st.update_ms), float(st.loss_ms))
+
+    def ials_loss(self, user, item, conf, n_users, n_items, U, V, *, pref=None, lam=0.1, reg_user=None,
+                  reg_item=None) -> float:
+        """cf_ials_loss: the implicit-feedback loss of any factors over the whole grid."""
+        n_users, n_items = int(n_users), int(n_items)
+        (U, V), D = _mf_factors((U, V), (n_users, n_items), "U and V", "U / V")
+        g = self._ials_graph(user, item, conf, pref, n_users, n_items, lam, reg_user, reg_item)
+        out = c_double()
+        self._chk(self.lib.cf_ials_loss(self.h, n_users, n_items, int(D), *[ptr(x) for x in g], ptr(U), ptr(V),
+                                        byref(out)), "cf_ials_loss")
+        return out.value
+
+    def mf_gram(self, F) -> np.ndarray:
+        """cf_mf_gram: F^T F (D x D) of an n x D matrix, summed in slices of fixed length."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.ndim != 2 or F.shape[1] == 0:
+            raise ValueError("F must be n x D with D >= 1")
+        G = np.zeros((F.shape[1], F.shape[1]), dtype=np.float64)
+        self._chk(self.lib.cf_mf_gram(self.h, F.shape[0], F.shape[1], ptr(F), ptr(G)), "cf_mf_gram")
+        return G
 
     # -- SGD / bias-SGD matrix factorization (sgd.cpp, biassgd.cpp) ----------------------
     def sgd_fit(self, user, item, obs, n_users, n_items, U0, V0, *, bias=False, lam=0.001, gamma=0.001, step_dec=0.9,

@@ -31,10 +31,11 @@
 // are active and however often a fit is repeated.  (The Gram kernels below implement the rule
 // for ALS; SGD and SVD++ share one implementation of it, cf_mf_reduce.h.)
 //
-// The Gram of one wave: D is padded to DP = 8 / 16 / 32 / 64 and lane l owns the TS x TS block
-// (TS = DP / 8) at block row l >> 3, block column l & 7 of A, in registers; neighbour rows are
-// staged kBatch at a time (coalesced) in wave-private LDS and every lane reads its 2 TS values
-// per neighbour from there.  Each element is one fma chain in CSR order.
+// The Gram of one wave and the solve are in cf_als_gram.h (shared with cf_ials.hip): D is padded
+// to DP = 8 / 16 / 32 / 64 and lane l owns the TS x TS block (TS = DP / 8) at block row l >> 3,
+// block column l & 7 of A, in registers; neighbour rows are staged kBatch at a time (coalesced)
+// in wave-private LDS and every lane reads its 2 TS values per neighbour from there.  Each
+// element is one fma chain in CSR order.
 // The solve is an unpivoted LDL^T of the packed lower triangle (= the upper triangle the
 // reference factors, als.cpp:330) with b carried as a border row (the layout of cf_ldlt.hpp),
 // done by one wave in LDS for D <= 64.  An exactly zero pivot is skipped as cf_ldlt.hpp
@@ -45,15 +46,11 @@
 #include <algorithm>
 #include <cmath>
 
+#include "cf_als_gram.h"
 #include "cf_internal.h"
-#include "cf_ldlt.hpp"
 #include "cf_mf_common.h"
 
 namespace {
-
-constexpr int kBatch = 16;             // neighbour rows staged per wave at a time
-
-__host__ __device__ constexpr int sys_len(int D) { return (D + 1) * (D + 2) / 2; }   // packed rows 0..D
 
 // One side of the graph as the kernels see it.
 struct AlsSide {
@@ -69,118 +66,6 @@ struct AlsSide {
     uint8_t* flag;         // signalled for the next superstep of this side
     uint8_t* active;       // active in the current superstep of this side
 };
-
-template <int DP>
-struct Gram {
-    static constexpr int TS = DP / 8;
-    double a[TS][TS];
-    double b[TS];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int x = 0; x < TS; ++x) {
-            b[x] = 0.0;
-#pragma unroll
-            for (int y = 0; y < TS; ++y) a[x][y] = 0.0;
-        }
-    }
-};
-
-// A += sum x x^T, b += sum obs x over the edges [p0, p1) in order; stage: kBatch * DP doubles of
-// wave-private LDS.  Called by a whole wave.
-template <int DP>
-__device__ __forceinline__ void gram_accumulate(Gram<DP>& g, double* stage, const double* __restrict__ Fo, int D,
-                                                const uint32_t* __restrict__ nbr, const float* __restrict__ obs,
-                                                uint64_t p0, uint64_t p1, int lane) {
-    constexpr int TS = DP / 8;
-    const int ti = lane >> 3, tj = lane & 7;
-    for (uint64_t p = p0; p < p1; p += kBatch) {
-        const int nb = (int)(p1 - p < (uint64_t)kBatch ? p1 - p : (uint64_t)kBatch);
-#pragma unroll
-        for (int r = 0; r < kBatch * DP / 64; ++r) {
-            const int t = lane + 64 * r;
-            const int k = t / DP, d = t % DP;
-            double v = 0.0;
-            if (k < nb && d < D) v = Fo[(size_t)nbr[p + k] * D + d];
-            stage[t] = v;
-        }
-        const float ob = lane < nb ? obs[p + lane] : 0.0f;
-        WAVE_SYNC();
-        for (int k = 0; k < nb; ++k) {
-            double xi[TS], xj[TS];
-#pragma unroll
-            for (int x = 0; x < TS; ++x) {
-                xi[x] = stage[k * DP + ti * TS + x];
-                xj[x] = stage[k * DP + tj * TS + x];
-            }
-            const double o = (double)__shfl(ob, k);
-#pragma unroll
-            for (int x = 0; x < TS; ++x) {
-#pragma unroll
-                for (int y = 0; y < TS; ++y) g.a[x][y] = fma(xi[x], xj[y], g.a[x][y]);
-                g.b[x] = fma(o, xi[x], g.b[x]);
-            }
-        }
-        WAVE_SYNC();
-    }
-}
-
-// The wave's partial into the packed system S (rows 0..D-1 = lower triangle of A, row D = b).
-template <int DP, bool ADD>
-__device__ __forceinline__ void gram_to_system(const Gram<DP>& g, double* S, int D, int lane) {
-    constexpr int TS = DP / 8;
-    const int ti = lane >> 3, tj = lane & 7;
-#pragma unroll
-    for (int x = 0; x < TS; ++x) {
-        const int i = ti * TS + x;
-#pragma unroll
-        for (int y = 0; y < TS; ++y) {
-            const int q = tj * TS + y;
-            if (i < D && q <= i) {
-                const int idx = tri(i, q);
-                S[idx] = ADD ? S[idx] + g.a[x][y] : g.a[x][y];
-            }
-        }
-        if (tj == 0 && i < D) {
-            const int idx = tri(D, i);
-            S[idx] = ADD ? S[idx] + g.b[x] : g.b[x];
-        }
-    }
-}
-
-// Unpivoted LDL^T of the D x D system in S with b as the border row D, then L^T x = y: on
-// return S[tri(D, d)] = x_d.  One wave; S is LDS.  Returns the number of pivots that are not > 0.
-__device__ inline int wave_ldlt_solve(double* S, int D, double reg, int lane) {
-    for (int i = lane; i < D; i += 64) S[tri(i, i)] += reg;
-    WAVE_SYNC();
-    int not_pd = 0;
-    for (int j = 0; j < D; ++j) {
-        const double dj = S[tri(j, j)];
-        if (!(dj > 0.0)) ++not_pd;
-        // trailing update of rows j+1..D with the unscaled column j
-        for (int i = j + 1 + lane; i <= D; i += 64) {
-            const double w = S[tri(i, j)];
-            const double lij = dj != 0.0 ? w / dj : 0.0;   // exact-zero pivot: skipped
-            const int qe = i < D ? i : D - 1;
-            double* Si = S + tri(i, 0);
-            for (int q = j + 1; q <= qe; ++q) Si[q] = fma(-lij, S[tri(q, j)], Si[q]);
-        }
-        WAVE_SYNC();
-        for (int i = j + 1 + lane; i <= D; i += 64) {
-            const double w = S[tri(i, j)];
-            S[tri(i, j)] = dj != 0.0 ? w / dj : 0.0;
-        }
-        WAVE_SYNC();
-    }
-    // border row = y = D^-1 L^-1 b; back substitution, column by column
-    double* y = S + tri(D, 0);
-    for (int i = D - 1; i > 0; --i) {
-        const double xi = y[i];
-        const double* Li = S + tri(i, 0);
-        for (int k = lane; k < i; k += 64) y[k] = fma(-Li[k], xi, y[k]);
-        WAVE_SYNC();
-    }
-    return not_pd;
-}
 
 // apply's tail for vertex v with the system in S: solve, residual, store.  One wave.
 __device__ inline void wave_apply(double* S, int D, const AlsSide& s, uint32_t v, unsigned long long* not_pd,
@@ -200,11 +85,6 @@ __device__ inline void wave_apply(double* S, int D, const AlsSide& s, uint32_t v
         s.nupd[v] += 1;
         if (bad) atomicAdd(not_pd, (unsigned long long)bad);   // integer counter
     }
-}
-
-template <int DP>
-constexpr int low_region() {   // doubles of LDS per wave: the staging rows, then the system in their place
-    return ((kBatch * DP > sys_len(DP) ? kBatch * DP : sys_len(DP)) + 1) & ~1;
 }
 
 // low class: one wave per vertex.
@@ -228,15 +108,10 @@ __global__ __launch_bounds__(kAT) void als_low_kernel(AlsSide s, const double* _
     double* R = lds + wave * low_region<DP>();
     Gram<DP> g;
     g.clear();
-    gram_accumulate<DP>(g, R, Fo, D, s.nbr, s.obs, p0, p1, lane);
+    gram_accumulate<DP, false>(g, R, Fo, D, s.nbr, s.obs, nullptr, p0, p1, lane);
     gram_to_system<DP, false>(g, R, D, lane);
     WAVE_SYNC();
     wave_apply(R, D, s, v, not_pd, lane);
-}
-
-template <int DP>
-constexpr int mid_region() {
-    return ((kWaves * kBatch * DP > sys_len(DP) ? kWaves * kBatch * DP : sys_len(DP)) + 1) & ~1;
 }
 
 // mid class (SEGMENT = false): one workgroup per vertex, solved here.  high class (SEGMENT =
@@ -261,7 +136,7 @@ __global__ __launch_bounds__(kAT) void als_group_kernel(AlsSide s, const double*
     const uint64_t b = std::min(len, wave * chunk), e = std::min(len, (wave + 1) * chunk);
     Gram<DP> g;
     g.clear();
-    gram_accumulate<DP>(g, lds + wave * kBatch * DP, Fo, D, s.nbr, s.obs, p0 + b, p0 + e, lane);
+    gram_accumulate<DP, false>(g, lds + wave * kBatch * DP, Fo, D, s.nbr, s.obs, nullptr, p0 + b, p0 + e, lane);
     __syncthreads();   // the staging rows are dead: the system takes their place
     if (wave == 0) gram_to_system<DP, false>(g, lds, D, lane);
     __syncthreads();

@@ -176,8 +176,9 @@ __device__ __forceinline__ double mf_clamp(double p, double minval, double maxva
     return fmax(minval, p);
 }
 
-// pred[e] of the pairs (user[e], item[e]); clamped iff clamp != 0.
-__global__ __launch_bounds__(kAT) void mf_predict_kernel(uint64_t n, const uint32_t* __restrict__ user,
+// pred[e] of the pairs (user[e], item[e]); clamped iff clamp != 0.  (Not every file that includes
+// this header predicts: cf_ials.hip leaves it unused.)
+__attribute__((unused)) __global__ __launch_bounds__(kAT) void mf_predict_kernel(uint64_t n, const uint32_t* __restrict__ user,
                                                         const uint32_t* __restrict__ item, const double* __restrict__ U,
                                                         const double* __restrict__ V, int D, const double* __restrict__ bu,
                                                         const double* __restrict__ bi, double mean, int clamp,

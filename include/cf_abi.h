@@ -779,6 +779,52 @@ int cf_set_topn_block(cf_ctx* ctx, uint32_t users_per_block);
 int cf_debug_topn_tile_users(void);
 int cf_debug_topn_tile_items(void);
 
+/* ---- implicit-feedback ALS (Hu, Koren, Volinsky, ICDM 2008; no reference counterpart: wals.cpp
+ * cites the paper and fits observed and sampled edges only) ----
+ * Every pair of the n_users x n_items grid is a training example: an edge carries a confidence
+ * conf >= 1 and a preference pref (both f32 per edge; repeated edges each count), every other pair
+ * is pref 0 with confidence 1.
+ *   L(U, V) = sum_{u,i} c_ui (p_ui - U_u.V_i)^2 + sum_u reg_user[u] |U_u|^2 + sum_i reg_item[i] |V_i|^2
+ * A sweep is a user half-sweep, then an item half-sweep; a half-sweep sets every vertex v of its
+ * side to the exact minimiser: with x the other side's rows and G = sum over all of them of x x^T,
+ *   (G + sum_{edges of v} (c - 1) x x^T + reg[v] I) f = sum_{edges of v} (c p) x
+ * by the unpivoted LDL^T of cf_als_fit (reg > 0 and c >= 1 make every system positive definite;
+ * n_not_pd counts pivots <= 0).  A vertex without edges becomes +0.0 in every component.
+ * fp64 throughout and no floating-point atomics: a vertex's new factor depends only on its own edge
+ * list, the other side's rows and the bits of G; a repeated fit gives the same bytes.
+ *   user_off / user_item / user_conf / user_pref : CSR over users; item_* : its transpose (checked
+ *       like cf_als_fit's).  Both pref arrays NULL = every preference is 1; exactly one NULL is
+ *       CF_EINVAL, as are a conf < 1 or not finite and a pref not finite
+ *   U [n_users * D], V [n_items * D] : in the initial factors, out the fitted ones
+ *   loss_trace : NULL, or 2 * n_sweeps doubles: L after each half-sweep
+ * D == 0 gives CF_EINVAL, D > CF_ALS_MAX_D CF_ERANGE; n_sweeps == 0 (U, V untouched), no edges and an
+ * empty side are valid calls. */
+typedef struct cf_ials_stats {
+    uint32_t sweeps;       /* sweeps run */
+    uint64_t n_not_pd;     /* pivots <= 0 met by the solves */
+    float gram_ms;         /* device time of the global Gram kernels (HIP events) */
+    float update_ms;       /* device time of the per-vertex update kernels */
+    float loss_ms;         /* device time of the loss kernels (0 without a trace) */
+} cf_ials_stats;
+int cf_ials_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+                const uint32_t* user_item, const float* user_conf, const float* user_pref, const uint64_t* item_off,
+                const uint32_t* item_user, const float* item_conf, const float* item_pref, const double* reg_user,
+                const double* reg_item, uint32_t n_sweeps, double* U, double* V, double* loss_trace,
+                cf_ials_stats* stats);
+/* *loss = L(U, V) of any factors, evaluated without the unobserved pairs:
+ * <U^T U, V^T V>_F + sum over the edges of [c (p - s)^2 - s^2] + the two reg terms, s = U_u.V_i.
+ * Fixed reductions: the same inputs give the same bits.  Arguments and checks as cf_ials_fit. */
+int cf_ials_loss(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+                 const uint32_t* user_item, const float* user_conf, const float* user_pref, const uint64_t* item_off,
+                 const uint32_t* item_user, const float* item_conf, const float* item_pref, const double* reg_user,
+                 const double* reg_item, const double* U, const double* V, double* loss);
+/* G [D * D] = F^T F of the n x D row-major matrix F: slices of cf_debug_ials_gram_rows() rows, summed
+ * in slice order; a slice's partial depends on its own rows only.  G is symmetric bit for bit and the
+ * same bits in every run; appending rows that are all zero does not change it.  n == 0 gives zeros. */
+int cf_mf_gram(cf_ctx* ctx, uint32_t n, uint32_t D, const double* F, double* G);
+/* The slice length of the global Gram (a constant of cf_ials.hip; test helper, needs no GPU). */
+int cf_debug_ials_gram_rows(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,216 @@
+"""Implicit-feedback ALS on the GPU (cf_ials_fit / cf_ials_loss / cf_mf_gram) against the dense
+numpy checker tests/ials_ref.py, which does not use the Gram trick.
+
+How the bounds were measured (tools/ials_drift.py, CPU): the checker against itself on these
+cases with the edge order permuted and the initial factors perturbed by 1e-15 relative drifts by
+at most 3.2e-14 * max|factor| in the factors (case B, the worst conditioned: lambda_min /
+lambda_max = 2e-3) and 1.3e-15 relative in a loss-trace entry; numpy's F^T F against itself with
+the rows permuted and perturbed drifts by 2.2e-15 of |F|^T |F| elementwise (1 to 20,481 rows).  The bounds leave the
+few-hundred-fold margin test_gpu_als.py documents (about 300 x) for another summation tree and an
+unpivoted factorisation:
+    factors  1e-11 * max|factor|        loss  4e-13 relative        Gram  6.5e-13 * |F|^T |F|"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import ials_ref as ir
+from collaborative_filtering_amd import _native
+from collaborative_filtering_amd._native import ptr
+
+pytestmark = pytest.mark.gpu
+
+FACTOR_BOUND = 1e-11
+LOSS_BOUND = 4e-13
+GRAM_BOUND = 6.5e-13
+_FITS = {}
+
+
+def device_fit(ctx, c: ir.Case, n_sweeps=ir.N_SWEEPS, **over):
+    kw = dict(pref=c.pref, reg_user=c.reg_user, reg_item=c.reg_item, n_sweeps=n_sweeps)
+    kw.update(over)
+    return ctx.ials_fit(c.user, c.item, c.conf, c.n_users, c.n_items, c.U0, c.V0, **kw)
+
+
+def case_fit(ctx, name):
+    """The device's run of a case, computed once and shared (not modified by the tests)."""
+    if name not in _FITS:
+        _FITS[name] = device_fit(ctx, ir.case_inputs(name))
+    return _FITS[name]
+
+
+def check_against(name, c, r, ref):
+    assert r.sweeps == ir.N_SWEEPS and r.n_not_pd == 0
+    for got, want in ((r.U, ref.U), (r.V, ref.V)):
+        err = np.max(np.abs(got - want))
+        print(name, "max|dF|", err, "max|F|", np.max(np.abs(want)))
+        assert err <= FACTOR_BOUND * np.max(np.abs(want))
+    rel = np.abs(r.loss_trace - ref.loss_trace) / np.abs(ref.loss_trace)
+    print(name, "loss", r.loss_trace, "relative error", rel)
+    assert r.loss_trace.shape == (2 * ir.N_SWEEPS,) and np.all(rel <= LOSS_BOUND)
+    # vertices without edges: exactly +0.0 in every component
+    for F, idx, n in ((r.U, c.user, c.n_users), (r.V, c.item, c.n_items)):
+        empty = np.bincount(idx, minlength=n) == 0
+        assert not np.any(F[empty]) and not np.any(np.signbit(F[empty]))
+
+
+@pytest.mark.parametrize("name", list(ir.CASES))
+def test_case_matches_checker(gpu_ctx, name):
+    lib = _native.load()
+    c, ref = ir.case_inputs(name), ir.case_reference(name)
+    deg_i, deg_u = np.bincount(c.item, minlength=c.n_items), np.bincount(c.user, minlength=c.n_users)
+    # conditions on the input, not on the device
+    assert ref.min_eig_ratio >= 1e-3, ref.min_eig_ratio
+    assert deg_u.min() == 0 and deg_i.min() == 0                       # a user without edges, an item nobody rated
+    assert np.any(c.conf != np.round(c.conf)) and (c.pref is None or (np.any(c.pref == 0) and np.any(c.pref == 1)))
+    if name in ("A", "B"):
+        assert deg_i.max() > lib.cf_debug_als_low_max() >= deg_i[deg_i > 0].min()   # wave and workgroup paths
+    if name == "H":
+        assert deg_i.max() > lib.cf_debug_als_segment()                             # the segment path
+    check_against(name, c, case_fit(gpu_ctx, name), ref)
+
+
+def test_loss_trace_decreases(gpu_ctx):
+    for name in ir.CASES:
+        ref, r = ir.case_reference(name), case_fit(gpu_ctx, name)
+        drop = -np.diff(ref.loss_trace) / ref.loss_trace[:-1]
+        assert np.all(drop >= 0)                      # the checker's trace is non-increasing
+        strict = drop >= 1e-6
+        assert strict.any()
+        assert np.all(np.diff(r.loss_trace)[strict] < 0)
+
+
+def test_loss_of_any_factors(gpu_ctx):
+    c, r = ir.case_inputs("A"), case_fit(gpu_ctx, "A")
+    rng = np.random.default_rng(2)
+    for U, V in ((c.U0, c.V0), (3.0 * r.U, r.V), (r.U * (1 + 0.1 * rng.uniform(-1, 1, r.U.shape)), -0.5 * r.V)):
+        want = ir.loss(c.user, c.item, c.conf, c.pref, c.n_users, c.n_items, U, V, c.reg_user, c.reg_item)
+        got = gpu_ctx.ials_loss(c.user, c.item, c.conf, c.n_users, c.n_items, U, V, pref=c.pref, reg_user=c.reg_user,
+                                reg_item=c.reg_item)
+        print("loss", got, want, abs(got - want) / want)
+        assert abs(got - want) <= LOSS_BOUND * want
+        again = gpu_ctx.ials_loss(c.user, c.item, c.conf, c.n_users, c.n_items, U, V, pref=c.pref, reg_user=c.reg_user,
+                                  reg_item=c.reg_item)
+        assert np.float64(got).tobytes() == np.float64(again).tobytes()
+    # the loss the fit traced last is the loss of the factors it returned
+    got = gpu_ctx.ials_loss(c.user, c.item, c.conf, c.n_users, c.n_items, r.U, r.V, pref=c.pref, reg_user=c.reg_user,
+                            reg_item=c.reg_item)
+    assert np.float64(got).tobytes() == r.loss_trace[-1].tobytes()
+
+
+def test_gram(gpu_ctx):
+    R = _native.load().cf_debug_ials_gram_rows()
+    rng = np.random.default_rng(6)
+    worst = 0.0
+    for n in (1, R - 1, R, R + 1, 2 * R + 3):
+        for D in (1, 5, 20, 33, 64):
+            F = rng.uniform(-1, 1, (n, D))
+            G = gpu_ctx.mf_gram(F)
+            scale = np.abs(F).T @ np.abs(F)
+            worst = max(worst, float(np.max(np.abs(G - F.T @ F) / scale)))
+            assert np.all(np.abs(G - F.T @ F) <= GRAM_BOUND * scale), (n, D)
+            assert G.tobytes() == np.ascontiguousarray(G.T).tobytes(), (n, D)          # symmetric bit for bit
+            assert gpu_ctx.mf_gram(F).tobytes() == G.tobytes(), (n, D)                  # the same bytes on repeat
+            if n == R + 1:   # rows of zeros appended to the last slice and as new slices change nothing
+                assert gpu_ctx.mf_gram(np.vstack([F, np.zeros((R + 7, D))])).tobytes() == G.tobytes(), D
+    for D in (5, 33):   # more slices than the slice-order sum loads ahead (32): both of its loops run
+        F = rng.uniform(-1, 1, (40 * R + 1, D))
+        G = gpu_ctx.mf_gram(F)
+        scale = np.abs(F).T @ np.abs(F)
+        worst = max(worst, float(np.max(np.abs(G - F.T @ F) / scale)))
+        assert np.all(np.abs(G - F.T @ F) <= GRAM_BOUND * scale), D
+        assert G.tobytes() == np.ascontiguousarray(G.T).tobytes() and gpu_ctx.mf_gram(F).tobytes() == G.tobytes()
+    print("worst Gram error relative to |F|^T |F|", worst)
+    assert not np.any(gpu_ctx.mf_gram(np.zeros((0, 4))))
+
+
+def test_fit_with_a_gram_of_two_slices(gpu_ctx):
+    R = _native.load().cf_debug_ials_gram_rows()
+    c = ir.gram_fit_case(R)
+    assert c.n_items == R + 1 and c.n_users == 8
+    pairs = c.user.astype(np.int64) * c.n_items + c.item
+    assert len(np.unique(pairs)) == len(pairs) - 1       # one repeated edge
+    ref = ir.fit_case(c)
+    assert ref.min_eig_ratio >= 1e-3
+    check_against("G", c, device_fit(gpu_ctx, c), ref)
+
+
+def test_repeat_is_bit_identical(gpu_ctx):
+    for name in ("A", "H"):
+        a, b = case_fit(gpu_ctx, name), device_fit(gpu_ctx, ir.case_inputs(name))
+        for x, y in ((a.U, b.U), (a.V, b.V), (a.loss_trace, b.loss_trace)):
+            assert x.tobytes() == y.tobytes()
+
+
+def test_heavy_item_is_independent_of_other_vertices(gpu_ctx):
+    """Case H's item 0 (above the segment length) with the edges of every other item removed
+    from the graph: its own edge list, the users' rows and their Gram are unchanged, so its new
+    factor is the same bytes.  The roles are swapped (items passed as the first side) so that the
+    heavy vertex is updated in the first half-sweep, straight from the initial factors."""
+    c = ir.case_inputs("H")
+    keep = c.item == 0
+    assert keep.sum() > _native.load().cf_debug_als_segment()
+    a = gpu_ctx.ials_fit(c.item, c.user, c.conf, c.n_items, c.n_users, c.V0, c.U0, pref=c.pref, reg_user=c.reg_item,
+                         reg_item=c.reg_user, n_sweeps=1, trace=False)
+    b = gpu_ctx.ials_fit(c.item[keep], c.user[keep], c.conf[keep], c.n_items, c.n_users, c.V0, c.U0,
+                         pref=c.pref[keep], reg_user=c.reg_item, reg_item=c.reg_user, n_sweeps=1, trace=False)
+    assert a.U[0].tobytes() == b.U[0].tobytes() and np.any(a.U[0])
+    assert a.U[1:].tobytes() != b.U[1:].tobytes()         # the other items did change
+
+
+def test_argument_checks(gpu_ctx):
+    lib, h = gpu_ctx.lib, gpu_ctx.h
+    u64, u32, f32 = np.uint64, np.uint32, np.float32
+
+    def call(n_users, n_items, D, uoff, uitem, ioff, iuser, conf=None, upref=None, ipref=None, n_sweeps=1, U=None,
+             V=None):
+        nnz = len(uitem)
+        conf = np.full(max(nnz, 1), 2.0, f32) if conf is None else conf
+        U = np.ones((max(n_users, 1), D)) if U is None else U
+        V = np.ones((max(n_items, 1), D)) if V is None else V
+        reg = np.full(max(n_users, n_items, 1), 0.1)
+        st = _native.IalsStats()
+        return lib.cf_ials_fit(h, n_users, n_items, D, ptr(uoff), ptr(uitem), ptr(conf), ptr(upref), ptr(ioff),
+                               ptr(iuser), ptr(conf), ptr(ipref), ptr(reg), ptr(reg), n_sweeps, ptr(U), ptr(V), None,
+                               ctypes.byref(st)), st
+
+    uoff, uitem = np.array([0, 1, 2], u64), np.array([0, 0], u32)
+    ioff, iuser = np.array([0, 2], u64), np.array([0, 1], u32)
+    ones = np.ones(2, f32)
+    rc, st = call(2, 1, 4, uoff, uitem, ioff, iuser)
+    assert rc == _native.CF_OK and st.sweeps == 1 and st.n_not_pd == 0
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, upref=ones, ipref=ones)[0] == _native.CF_OK
+    assert call(2, 1, 65, uoff, uitem, ioff, iuser)[0] == _native.CF_ERANGE
+    assert call(2, 1, 0, uoff, uitem, ioff, iuser)[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, conf=np.array([2.0, 0.5], f32))[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, conf=np.array([np.nan, 2.0], f32))[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, conf=np.array([np.inf, 2.0], f32))[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, upref=ones)[0] == _native.CF_EINVAL            # exactly one pref
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, ipref=ones)[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, ioff, iuser, upref=np.array([1.0, np.inf], f32), ipref=ones)[0] == _native.CF_EINVAL
+    assert call(2, 1, 4, uoff, uitem, np.array([0, 1], u64), iuser)[0] == _native.CF_EINVAL       # edge totals differ
+    assert call(2, 2, 4, uoff, uitem, np.array([0, 1, 2], u64), iuser)[0] == _native.CF_EINVAL    # per-item counts differ
+    # n_sweeps = 0 leaves U and V untouched
+    U, V = np.arange(8.0).reshape(2, 4), np.arange(4.0).reshape(1, 4)
+    rc, st = call(2, 1, 4, uoff, uitem, ioff, iuser, n_sweeps=0, U=U, V=V)
+    assert rc == _native.CF_OK and st.sweeps == 0
+    assert np.array_equal(U, np.arange(8.0).reshape(2, 4)) and np.array_equal(V, np.arange(4.0).reshape(1, 4))
+    # an empty graph, no edges, an empty side
+    assert call(0, 0, 4, np.zeros(1, u64), np.zeros(0, u32), np.zeros(1, u64), np.zeros(0, u32))[0] == _native.CF_OK
+    U = np.ones((2, 4))
+    rc, st = call(2, 1, 4, np.zeros(3, u64), np.zeros(0, u32), np.zeros(2, u64), np.zeros(0, u32), U=U)
+    assert rc == _native.CF_OK and st.sweeps == 1 and not np.any(U)      # b = 0 everywhere
+    V = np.ones((3, 4))
+    rc, st = call(0, 3, 4, np.zeros(1, u64), np.zeros(0, u32), np.zeros(4, u64), np.zeros(0, u32), V=V)
+    assert rc == _native.CF_OK and not np.any(V)
+
+
+def test_python_layer(gpu_ctx):
+    r = gpu_ctx.ials_fit([], [], [], 0, 0, np.zeros((0, 4)), np.zeros((0, 4)), n_sweeps=2)
+    assert r.U.shape == (0, 4) and r.V.shape == (0, 4)
+    c = ir.case_inputs("B8")
+    with pytest.raises(_native.NativeError):
+        gpu_ctx.ials_fit(c.user, c.item, 0.5 * c.conf, c.n_users, c.n_items, c.U0, c.V0, n_sweeps=1)
+    r = gpu_ctx.ials_fit(c.user, c.item, c.conf, c.n_users, c.n_items, c.U0, c.V0, pref=c.pref, reg_user=c.reg_user,
+                         reg_item=c.reg_item, n_sweeps=ir.N_SWEEPS, trace=False)
+    assert r.loss_trace.size == 0 and r.U.tobytes() == case_fit(gpu_ctx, "B8").U.tobytes()
