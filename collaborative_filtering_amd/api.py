@@ -299,6 +299,11 @@ class Context:
         True the default buckets, or an int 5..12 = the smallest bucket that takes it."""
         self._chk(self.lib.cf_set_eigen_split(self.h, int(enable)), "cf_set_eigen_split")
 
+    def set_pred_pack(self, mode=1):
+        """Predictor fast path: small per-rating systems two or four to a wave (cf_set_pred_pack):
+        1 on (default), 0 one rating per wave.  Same output bits either way."""
+        self._chk(self.lib.cf_set_pred_pack(self.h, int(mode)), "cf_set_pred_pack")
+
     def set_local_wlim(self, bisect: bool = True):
         """local_calc spill pairs: w_lim by bisection on the movie's B = L2 L2^T (cf_set_local_wlim)."""
         self._chk(self.lib.cf_set_local_wlim(self.h, int(bisect)), "cf_set_local_wlim")
@@ -358,7 +363,7 @@ class Context:
         self._chk(self.lib.cf_debug_phases(self.h, int(enable), ptr(out)), "cf_debug_phases")
         if read:
             names = ["setup", "basis", "fast", "dense", "n_fast", "n_dense", "gram", "wide",
-                     "w_gather", "w_ldlt", "w_fast", "cyc_nc4", "cyc_nc16", "cyc_ncbig", "n_nc4", "n_nc16"]
+                     "w_gather", "w_ldlt", "w_fast", "cyc_n14", "cyc_n30", "cyc_nbig", "n_n14", "n_n30"]
             return dict(zip(names, map(int, out)))
         return None
 

@@ -39,7 +39,9 @@
 // pseudo-inverse solution).  Either system has min(nc, d) rows and is the Gram
 // matrix of gathered rows of X: fp64 MFMA on one wave (bordered by B h / e_r or w_r / h),
 // then the wave's bordered LDL^T.  A rating costs ~nc d min(nc, d) MFMA flops instead of a
-// lim x lim factorisation.
+// lim x lim factorisation.  Small systems share a wave (lane packing): up to
+// kQuadNMax rows four ratings per wave, up to kPairNMax rows two, with the same arithmetic per
+// rating (cf_set_pred_pack(0) gives every rating its own wave; the outputs are bit-identical).
 //
 // Dense path (block-wide, the rating's own Gram matrix) for the ratings the fast path
 // does not take: the column filter drops a column, min(nc, d) > nmax, c = 0, a pivot of
@@ -62,6 +64,15 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kNsysMax = 62;          // fast path: system rows (n + 2 border rows <= 64 lanes)
+// lane packing: systems of up to kQuadNMax rows run four to a wave (n + 2 <= 16 lanes each), up
+// to kPairNMax two to a wave (n + 2 <= 32 lanes each)
+constexpr int kQuadNMax = 14;
+constexpr int kPairNMax = 30;
+// doubles of a bordered fast-path system of n rows (packed lower triangle, two border rows)
+constexpr int fast_tri(int n) { return (n + 2) * (n + 3) / 2; }
+// doubles per wave of G packed systems of up to nG rows: each its triangle, then y and g
+// (nc + d <= nG + lmax, whichever of the two is the system's side)
+constexpr int pack_elems(int G, int nG, int lmax) { return G * (fast_tri(nG) + lmax + nG); }
 // fast path: smallest pivot of K = I - P_CbarCbar (its pivots bound the smallest
 // eigenvalue of U_CS^T U_CS in the Q basis, so this admits cond <~ 1e10, where the
 // reference's own explicit inverse is accurate to ~cond * eps; parity is tested to 1e8)
@@ -113,6 +124,7 @@ struct PredArgs {
     int lmax;              // Gram dimension bound of the launch (row stride of the bases)
     int nmax;              // fast path: largest system min(nc, d) on one wave
     int ew;                // doubles of per-wave fast-path scratch (system + y + g)
+    int pack;              // 1: small systems run two or four to a wave (cf_set_pred_pack)
     int a_elems;           // doubles of the rating kernel's shared factorisation region
     int big_lds;           // 1: the block-wide systems use the LDS region A
     int tail_basis;        // 1: the last joint step writes only X's columns from Lmin on
@@ -147,6 +159,9 @@ __device__ __forceinline__ double row16_sum(double v) {
     v += dpp_f64<0x140>(v);   // row_mirror
     return v;
 }
+__device__ __forceinline__ double lane_f64(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 #ifdef CF_PRED_SHFL_SUM   // A/B: the LDS-permute butterfly (six dependent ds_bpermute pairs)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -154,9 +169,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 #else
-__device__ __forceinline__ double lane_f64(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 // Sum over the wave, the same bits in every lane: a butterfly inside each row of 16 (quad
 // permutes xor 1 and xor 2, then the half-row and row mirrors pair the quads and the halves;
 // each pair adds the same two operands in both lanes), then the four row sums in a fixed order.
@@ -926,6 +938,126 @@ constexpr size_t kRatingLds = 163840 / CF_PRED_RATING_OCC;
 #endif
 constexpr int kLdlPw = CF_PRED_LDL_PW;
 static_assert(kLdlPw == 4 || kLdlPw == 8, "panel width: one or two MFMA k-steps");
+
+// Fast-path LDL^T, the panel of columns [j0, j0 + pw) of the system in E (packed lower triangle,
+// n rows and the two border rows n, n + 1; nrows = n + 2): the lane that owns row `row`
+//  1. factors the pw x pw diagonal block in registers (every lane the same block, redundantly);
+//  2. writes its row of L and D if it is a row of the block, else solves its row against the
+//     block (its pw entries of L).
+// Dv: the block's pivots (1 past pw); minpiv takes their minimum.  A lane with !act reads (any
+// valid j0, pw of its system) and writes nothing.  An exactly zero pivot is skipped (its column
+// of L is 0), as in cf_ldlt.hpp.
+__device__ __forceinline__ void ldl_panel(double* E, int row, int nrows, int j0, int pw, bool act,
+                                          double (&Dv)[kLdlPw], double& minpiv) {
+    double Lm[kLdlPw][kLdlPw], Di[kLdlPw];
+#pragma unroll
+    for (int t = 0; t < kLdlPw; ++t) {
+        // unconditional (clamped) broadcast reads, then select
+        double at[kLdlPw];
+#pragma unroll
+        for (int u = 0; u <= t; ++u) at[u] = E[tri(j0 + min(t, pw - 1), j0 + min(u, pw - 1))];
+#pragma unroll
+        for (int u = 0; u <= t; ++u) at[u] = t < pw ? at[u] : (u == t ? 1.0 : 0.0);
+        // row t of the block against the rows above it (left-looking)
+#pragma unroll
+        for (int u = 0; u < t; ++u) {
+            double x = at[u];
+#pragma unroll
+            for (int s2 = 0; s2 < u; ++s2) x = fma(-Lm[t][s2] * Dv[s2], Lm[u][s2], x);
+            Lm[t][u] = x * Di[u];
+        }
+        double d = at[t];
+#pragma unroll
+        for (int s2 = 0; s2 < t; ++s2) d = fma(-Lm[t][s2] * Dv[s2], Lm[t][s2], d);
+        Dv[t] = d;
+        Di[t] = d != 0.0 ? pivot_rcp(d) : 0.0;   // exact-zero pivot: column skipped
+    }
+#pragma unroll
+    for (int t = 0; t < kLdlPw; ++t)
+        if (act && t < pw) minpiv = fmin(minpiv, Dv[t]);
+    if (act && row >= j0 && row < nrows) {
+        if (row < j0 + pw) {   // a row of the block: L and D from the factor
+#pragma unroll
+            for (int t = 0; t < kLdlPw; ++t)
+                if (row - j0 == t) {
+#pragma unroll
+                    for (int u = 0; u < t; ++u) E[tri(row, j0 + u)] = Lm[t][u];
+                    E[tri(row, row)] = Dv[t];
+                }
+        } else {   // a row below: z L11^T = a_i, l_i = z / D
+            double z[kLdlPw];
+#pragma unroll
+            for (int t = 0; t < kLdlPw; ++t) z[t] = E[tri(row, j0 + min(t, pw - 1))];
+#pragma unroll
+            for (int t = 0; t < kLdlPw; ++t) {
+                z[t] = t < pw ? z[t] : 0.0;
+#pragma unroll
+                for (int s2 = 0; s2 < t; ++s2) z[t] = fma(-z[s2], Lm[t][s2], z[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < kLdlPw; ++t)
+                if (t < pw) E[tri(row, j0 + t)] = z[t] * Di[t];
+        }
+    }
+}
+
+// The rank-pw trailing update A22 -= L21 D L21^T after ldl_panel, by the whole wave: one
+// v_mfma_f64_16x16x4 per 16 x 16 lower tile and 4 columns of the panel.  MFMA step s4 takes the
+// panel's columns 4 s4 .. 4 s4 + 3 (lane group lk): kc[s4] is this lane's column, dk[s4] its pivot.
+__device__ __forceinline__ void ldl_trailing(double* E, int n, int nrows, int j0, int pw,
+                                             const double (&dk)[kLdlPw / 4], const int (&kc)[kLdlPw / 4]) {
+    const int lane = threadIdx.x & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int r0 = j0 + pw;
+    const int ntr = (nrows - r0 + 15) >> 4, ntc = (n - r0 + 15) >> 4;
+    for (int ti = 0; ti < ntr; ++ti) {
+        const int arow = r0 + 16 * ti + li;
+        double aop[kLdlPw / 4];
+#pragma unroll
+        for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
+            const double av = E[tri(min(arow, nrows - 1), kc[s4])];
+            aop[s4] = (arow < nrows && 4 * s4 + lk < pw) ? -av * dk[s4] : 0.0;
+        }
+        const int tmax = min(ti, ntc - 1);
+        // two tiles of the row at a time: loads, then MFMAs, then stores
+        for (int tq0 = 0; tq0 <= tmax; tq0 += 2) {
+            f64x4 acc[2];
+            double bop[2][kLdlPw / 4];
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const int col = r0 + 16 * (tq0 + x) + li;
+#pragma unroll
+                for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
+                    const double bv = E[tri(min(col, n - 1), kc[s4])];
+                    bop[x][s4] = (col < n && 4 * s4 + lk < pw) ? bv : 0.0;
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = r0 + 16 * ti + lk + 4 * q;
+                    const int rc = min(row, nrows - 1);
+                    const double v = E[tri(rc, min(col, rc))];
+                    acc[x][q] = (tq0 + x <= tmax && row < nrows && col < n && col <= row) ? v : 0.0;
+                }
+            }
+#pragma unroll
+            for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
+                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s4], bop[0][s4], acc[0], 0, 0, 0);
+                if (tq0 + 1 <= tmax)
+                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s4], bop[1][s4], acc[1], 0, 0, 0);
+            }
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const int col = r0 + 16 * (tq0 + x) + li;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = r0 + 16 * ti + lk + 4 * q;
+                    if (tq0 + x <= tmax && row < nrows && col < n && col <= row) E[tri(row, col)] = acc[x][q];
+                }
+            }
+        }
+    }
+}
+
 // The dense path of one rating (row r, lim) of a user: the rating's own bordered Gram matrix
 // M = U_CS^T U_CS, blocked LDL^T, block-wide (local_calc_precomp.cpp:254-327).  Called by the
 // rating kernel's block for its user, or by pred_dense_kernel.  s_item / s_rat hold the user's
@@ -1153,29 +1285,302 @@ __device__ __forceinline__ void rating_user(const PredArgs<T> a, uint32_t uo, do
                 s_misc[1] = misc[0];
                 s_cnt[7] = 0;
                 s_cnt[8] = 0;
+                s_cnt[9] = 0;
+                s_cnt[10] = 0;
             }
         }
         __syncthreads();
         PHASE_STAMP(-1);
+
+        // Lane packing (a.pack): the order is split by system size n = min(nc, d) into three
+        // lists, each still largest nc first: single (one wave per rating: n > kPairNMax, n = 0,
+        // and what goes to the block-wide path before its Gram), pair (kQuadNMax < n <=
+        // kPairNMax: two ratings per wave, 32 lanes each) and quad (n <= kQuadNMax: four per
+        // wave, 16 lanes each).  s_conn / s_keep / s_nconn are free until the block-wide path.
+        const int* l_single = s_order;
+        int n_single = n_rate, n_pair = 0, n_quad = 0;
+        if (a.pack) {
+            int cls = 0;   // 0: none (not sampled), 1: single, 2: pair, 3: quad
+            int r = 0;
+            if (tid < n_rate) {
+                r = s_order[tid];
+                const int nc = __popcll(s_cmask[3 * r]) + __popcll(s_cmask[3 * r + 1]) + __popcll(s_cmask[3 * r + 2]);
+                const int d = k - s_lim[r];
+                const int n = min(nc, d);
+                const bool r_out = (s_cmask[3 * r + (r >> 6)] >> (r & 63)) & 1ull;
+                const bool pre_slow = k - nc == 0 || Lx == 0 || m < 2 || n > a.nmax || !r_out;
+                cls = (a.row_sel && !a.row_sel[base + r]) ? 0
+                      : (pre_slow || n > kPairNMax || n == 0) ? 1
+                      : n > kQuadNMax ? 2 : 3;
+            }
+            n_single = block_compact(cls == 1, r, s_conn, s_cnt);
+            n_pair = block_compact(cls == 2, r, s_keep, s_cnt);
+            n_quad = block_compact(cls == 3, r, s_nconn, s_cnt);
+            l_single = s_conn;
+        }
 
         // ---- fast path: one wave per rating, in the complement coordinates of its prefix --
         {
             double* Ew = A + (size_t)wave * a.ew;
             int* cb = s_cb + wave * CF_MAX_K;
             const double sum_all = s_misc[1];
-            // ratings are claimed from s_order one ahead (LDS counter)
-            auto claim = [&]() {
+            // ratings are claimed from a list `step` at a time, one claim ahead (LDS counter)
+            auto claim = [&](int* counter, int step) {
                 int v = 0;
-                if (lane == 0) v = atomicAdd(&s_cnt[8], 1);
+                if (lane == 0) v = atomicAdd(counter, step);
                 return __shfl(v, 0);
             };
             const unsigned long long fw0 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
             // diagnostics, summed over this wave's ratings of the user (wave-uniform)
             unsigned long long wacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            int idx = claim();
-            while (idx < n_rate) {
-                const int r = s_order[idx];
-                idx = claim();
+            // G ratings (cnt <= G of list[]; absent members masked) on this wave, 64 / G lanes
+            // each.  Every rating's arithmetic is that of the one-rating path below, operation
+            // for operation: the mask decode and the Gram use all 64 lanes, one member after
+            // another (the Gram's operand loads of all members in flight together); the border
+            // rows, the LDL^T panels and the final dot run in the member's own lane group, all
+            // groups at once; the trailing updates (matrix cores, all 64 lanes) follow one
+            // another.  A member's region of Ew: its system (fast_tri(NG) doubles), then y and g.
+            auto packed = [&](auto gconst, const int* list, int cnt) {
+                constexpr int G = decltype(gconst)::value;
+                constexpr int LG = 64 / G, NG = LG - 2, NS = LG / 16, NT = NS * (NS + 1) / 2;
+                // operand steps in flight per member: a trip to memory covers 4 PF terms of every
+                // member, as many as wave_gram's tile shapes take for one rating (no second buffer:
+                // the other members' loads are what a member's MFMAs overlap with)
+                constexpr int PF = 32 / (G * NS);
+                const int msz = pack_elems(1, NG, lmax);
+                uint8_t* cb8 = reinterpret_cast<uint8_t*>(cb);   // G lists of row indices (k <= 192)
+                const int grp = lane / LG, row = lane % LG;
+                const int li = lane & 15, lk = lane >> 4;
+                const unsigned long long rt0 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
+                // per member (wave-uniform); an absent or slow member is an empty system on row 0
+                int m_r[G], m_nc[G], m_lim[G], m_n[G], m_posr[G], m_inner[G];
+                bool m_k[G], m_ok[G];
+                double m_mu[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    uint8_t* cbg = cb8 + g * CF_MAX_K;
+                    m_ok[g] = g < cnt;
+                    m_r[g] = 0, m_nc[g] = 1, m_lim[g] = 0, m_n[g] = 0, m_posr[g] = 0, m_inner[g] = 0;
+                    m_k[g] = true;
+                    m_mu[g] = 0.0;
+                    if (m_ok[g]) {
+                        const int r = list[g];
+                        // Cbar in ascending row order (the position of r in it), its rating sum
+                        int nc = 0, posr = 0;
+                        double sc = 0.0;
+#pragma unroll
+                        for (int t = 0; t < 3; ++t) {
+                            const int i = 64 * t + lane;
+                            const unsigned long long bal = s_cmask[3 * r + t];
+                            if ((bal >> lane) & 1ull) {
+                                cbg[nc + __popcll(bal & ((1ull << lane) - 1ull))] = (uint8_t)i;
+                                sc += (double)s_rat[i];
+                            }
+                            if ((r >> 6) == t) posr = nc + __popcll(bal & ((1ull << (r & 63)) - 1ull));
+                            nc += __popcll(bal);
+                        }
+                        sc = wave_sum(sc);
+                        const int lim = s_lim[r];
+                        // column j < lim is dropped (:284-304) iff every row with U(i, j) >= 1e-4 lies in Cbar
+                        bool drop = false;
+                        const uint64_t c0 = ~s_cmask[3 * r], c1 = ~s_cmask[3 * r + 1], c2 = ~s_cmask[3 * r + 2];
+                        for (int j = lane; j < lim; j += 64)
+                            drop |= ((s_pmask[3 * j] & c0) | (s_pmask[3 * j + 1] & c1) | (s_pmask[3 * j + 2] & c2)) == 0ull;
+                        if (__ballot(drop) != 0ull) {   // a dropped column: the block-wide path
+                            if (lane == 0) s_slow[atomicAdd(&s_cnt[7], 1)] = r;
+                            m_ok[g] = false;
+                        } else {
+                            // the same in every lane: kept in scalar registers
+                            const auto uni = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
+                            m_r[g] = uni(r), m_nc[g] = uni(nc), m_lim[g] = uni(lim), m_posr[g] = uni(posr);
+                            const int d = k - m_lim[g];
+                            m_k[g] = m_nc[g] <= d;   // c >= lim: full rank
+                            m_n[g] = m_k[g] ? m_nc[g] : d;
+                            m_inner[g] = m_k[g] ? d : m_nc[g];
+                            m_mu[g] = lane_f64((sum_all - sc) / (double)(k - nc), 0);   // mean over C (:311)
+                        }
+                    }
+                    if (!m_ok[g] && lane == 0) cbg[0] = 0;
+                }
+                WAVE_SYNC();
+                const unsigned long long sp0 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
+                // y = r - mu on Cbar ([0, nc)) and g = (X^T r - mu X^T 1)[lim:k] ([nc, nc + d))
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    if (!m_ok[g]) continue;
+                    const uint8_t* cbg = cb8 + g * CF_MAX_K;
+                    double* aux = Ew + g * msz + fast_tri(NG);
+                    const double mu = m_mu[g];
+                    const int nc = m_nc[g], lim = m_lim[g], d = k - lim;
+                    for (int q = lane; q < nc; q += 64) aux[q] = (double)s_rat[cbg[q]] - mu;
+                    for (int j = lane; j < d; j += 64) aux[nc + j] = s_gx[lim + j] - mu * s_hx[lim + j];
+                }
+                WAVE_SYNC();
+                // The Gram of every member: rows {B, g^T} (K-mode) or columns {B, y} (G-mode), the
+                // k-steps in ascending order into one accumulator per tile as wave_gram_t does
+                {
+                    // the gathered entry of X (unconditional, clamped; a 32-bit offset from the
+                    // uniform base), and the operand it becomes: itself, the border operand, or 0
+                    const auto gather = [&](int g, int ar, int s) {
+                        const uint8_t* cbg = cb8 + g * CF_MAX_K;
+                        const int s2 = max(min(s, m_inner[g] - 1), 0), a2 = max(min(ar, m_n[g] - 1), 0);
+                        return Xf[(unsigned)(cbg[m_k[g] ? a2 : s2] * ld + m_lim[g] + (m_k[g] ? s2 : a2))];
+                    };
+                    const auto operand = [&](int g, int ar, int s, double vg) {
+                        const double* aux = Ew + g * msz + fast_tri(NG);
+                        const double vl = aux[(m_k[g] ? m_nc[g] : 0) + max(min(s, m_inner[g] - 1), 0)];
+                        return s < m_inner[g] ? (ar < m_n[g] ? vg : (ar == m_n[g] ? vl : 0.0)) : 0.0;
+                    };
+                    int imax = 0;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) imax = max(imax, m_inner[g]);
+                    f64x4 acc[G][NT];
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+#pragma unroll
+                        for (int x = 0; x < NT; ++x) acc[g][x] = f64x4{0.0, 0.0, 0.0, 0.0};
+                    double v[G][PF][NS];
+                    for (int s0 = 0; s0 < imax; s0 += 4 * PF) {
+#pragma unroll
+                        for (int g = 0; g < G; ++g)
+#pragma unroll
+                            for (int p = 0; p < PF; ++p)
+#pragma unroll
+                                for (int t = 0; t < NS; ++t) v[g][p][t] = gather(g, 16 * t + li, s0 + 4 * p + lk);
+#pragma unroll
+                        for (int p = 0; p < PF; ++p)
+#pragma unroll
+                            for (int g = 0; g < G; ++g) {
+                                if (s0 + 4 * p >= m_inner[g]) continue;   // wave-uniform
+                                double op[NS];
+#pragma unroll
+                                for (int t = 0; t < NS; ++t) op[t] = operand(g, 16 * t + li, s0 + 4 * p + lk, v[g][p][t]);
+                                int x = 0;
+#pragma unroll
+                                for (int ti = 0; ti < NS; ++ti)
+#pragma unroll
+                                    for (int tj = 0; tj <= ti; ++tj, ++x)
+                                        acc[g][x] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ti], op[tj], acc[g][x], 0, 0, 0);
+                            }
+                    }
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        double* E = Ew + g * msz;
+                        const int nt = m_ok[g] ? m_n[g] + 1 : 0;
+                        int x = 0;
+#pragma unroll
+                        for (int ti = 0; ti < NS; ++ti)
+#pragma unroll
+                            for (int tj = 0; tj <= ti; ++tj, ++x)
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    const int rw = 16 * ti + lk + 4 * q, col = 16 * tj + li;
+                                    if (rw < nt && col <= rw) E[tri(rw, col)] = acc[g][x][q];
+                                }
+                    }
+                }
+                WAVE_SYNC();
+                // from here on every lane works on its own group's member
+                int r = m_r[0], nc = m_nc[0], lim = m_lim[0], n = m_n[0], posr = m_posr[0];
+                bool kmode = m_k[0], ok = m_ok[0];
+                double mu = m_mu[0];
+#pragma unroll
+                for (int g = 1; g < G; ++g)
+                    if (grp == g) {
+                        r = m_r[g], nc = m_nc[g], lim = m_lim[g], n = m_n[g], posr = m_posr[g];
+                        kmode = m_k[g], ok = m_ok[g], mu = m_mu[g];
+                    }
+                double* E = Ew + grp * msz;
+                const double* yv = E + fast_tri(NG);
+                const double* gv = yv + nc;
+                // K-mode: b_a = (B g)_a - sum_q K_aq y_q into border row n, row n + 1 = e_r;
+                // G-mode: row n = w_r, row n + 1 = h = g - B^T y (row d of the Gram)
+                double ba = 0.0;
+                if (ok && kmode && row < n) {
+                    ba = E[tri(n, row)];
+                    for (int q = 0; q < n; ++q) {
+                        const double kq = q <= row ? E[tri(row, q)] : E[tri(q, row)];
+                        ba = fma(-kq, yv[q], ba);
+                    }
+                }
+                WAVE_SYNC();
+                if (ok && row < n) {
+                    if (kmode) {
+                        E[tri(n, row)] = ba;
+                        E[tri(n + 1, row)] = row == posr ? 1.0 : 0.0;
+                    } else {
+                        const double h = gv[row] - E[tri(n, row)];
+                        E[tri(n + 1, row)] = h;
+                        E[tri(n, row)] = Xf[(size_t)r * ld + lim + row];
+                    }
+                }
+                WAVE_SYNC();
+                const unsigned long long sp1 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
+                if (a.phase_cycles) wacc[0] += sp1 - sp0;
+                // LDL^T: the panels of all groups together, the trailing updates member by member.
+                // The other groups' lanes did not factor this member's block, so the operand scale
+                // of a trailing update is the stored pivot (the same bits as the factor's Dv).
+                int nmaxg = 0;
+#pragma unroll
+                for (int g = 0; g < G; ++g) nmaxg = max(nmaxg, m_ok[g] ? m_n[g] : 0);
+                double minpiv = 1.0;
+                for (int j0 = 0; j0 < nmaxg; j0 += kLdlPw) {
+                    const bool act = ok && j0 < n;
+                    double Dv[kLdlPw];
+                    ldl_panel(E, row, n + 2, act ? j0 : 0, act ? min(kLdlPw, n - j0) : 1, act, Dv, minpiv);
+                    WAVE_SYNC();
+#pragma nounroll   // one copy of the update's code: the member's n from its group's first lane
+                    for (int g = 0; g < G; ++g) {
+                        const int ng = __builtin_amdgcn_readlane(ok ? n : 0, g * LG), pw = min(kLdlPw, ng - j0);
+                        if (j0 + pw >= ng) continue;   // wave-uniform
+                        double* Eg = Ew + g * msz;
+                        double dk[kLdlPw / 4];
+                        int kc[kLdlPw / 4];
+#pragma unroll
+                        for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
+                            kc[s4] = j0 + min(4 * s4 + lk, pw - 1);
+                            dk[s4] = Eg[tri(kc[s4], kc[s4])];
+                        }
+                        ldl_trailing(Eg, ng, ng + 2, j0, pw, dk, kc);
+                    }
+                    WAVE_SYNC();
+                }
+                if (a.phase_cycles) wacc[1] += __builtin_amdgcn_s_memtime() - sp1;
+                // the final dot: the in-row butterfly of wave_sum, and for 32-lane groups the
+                // one add of the group's two row sums (wave_sum adds two zero rows after it)
+                double dot = 0.0;
+                if (ok && row < n) dot = E[tri(n, row)] * E[tri(n + 1, row)] * E[tri(row, row)];
+                dot = row16_sum(dot);
+                if (G == 2) {
+                    const double lo = lane_f64(dot, 0) + lane_f64(dot, 16), hi = lane_f64(dot, 32) + lane_f64(dot, 48);
+                    dot = grp == 0 ? lo : hi;
+                }
+                WAVE_SYNC();
+                if (ok && row == 0) {
+                    if (kmode && !(minpiv >= kPivMin)) {
+                        // full rank but ill-conditioned: the dense path, as the one-rating path
+                        s_slow[atomicAdd(&s_cnt[7], 1)] = r;
+                    } else {
+                        double pred = mu - dot;
+                        if (pred > 5) pred = 5;
+                        if (pred < 1) pred = 1;
+                        const double e = (double)s_rat[r] - pred;
+                        a.mse[base + r] = (float)(e * e);
+                        a.kk[base + r] = k - nc;
+                        if (a.pred) a.pred[base + r] = pred;
+                    }
+                }
+                if (a.phase_cycles) {   // the group's cycles and members under its class of n
+                    const unsigned long long dt = __builtin_amdgcn_s_memtime() - rt0;
+                    const int done = __popcll(__ballot(ok && row == 0 && !(kmode && !(minpiv >= kPivMin))));
+                    wacc[G == 4 ? 3 : 4] += dt;
+                    wacc[G == 4 ? 6 : 7] += done;
+                }
+            };
+            int idx = claim(&s_cnt[8], 1);
+            while (idx < n_single) {
+                const int r = l_single[idx];
+                idx = claim(&s_cnt[8], 1);
                 if (a.row_sel && !a.row_sel[base + r]) continue;   // movie not sampled (wave-uniform)
                 const unsigned long long rt0 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
                 // Cbar in ascending row order (the position of r in it), its rating sum
@@ -1273,74 +1678,18 @@ __device__ __forceinline__ void rating_user(const PredArgs<T> a, uint32_t uo, do
                 const unsigned long long sp1 = a.phase_cycles ? __builtin_amdgcn_s_memtime() : 0ull;
                 if (a.phase_cycles) wacc[0] += sp1 - sp0;
                 // LDL^T of the n x n system, border rows n and n + 1;
-                // lane i owns row i.  Panels of 4 columns, no per-column sync:
-                //  1. every lane factors the 4x4 diagonal block redundantly in registers;
-                //  2. each row below it solves against that block (its 4 entries of L);
-                //  3. the rank-4 trailing update A22 -= L21 D L21^T is one
-                //     v_mfma_f64_16x16x4 per 16x16 lower tile (k = 4 = the panel width).
-                // An exactly zero pivot is skipped (its column of L is 0), as in cf_ldlt.hpp.
+                // lane i owns row i.  Panels of kLdlPw columns, no per-column sync: the
+                // diagonal block and the row solves (ldl_panel), then the trailing update on
+                // the matrix cores (ldl_trailing).
                 const int nrows = n + 2;
                 double minpiv = 1.0;
-                const int li = lane & 15, lk = lane >> 4;
+                const int lk = lane >> 4;
                 for (int j0 = 0; j0 < n; j0 += kLdlPw) {
                     const int pw = min(kLdlPw, n - j0);
-                    double Lm[kLdlPw][kLdlPw], Dv[kLdlPw], Di[kLdlPw];
-#pragma unroll
-                    for (int t = 0; t < kLdlPw; ++t) {
-                        // unconditional (clamped) broadcast reads, then select
-                        double at[kLdlPw];
-#pragma unroll
-                        for (int u = 0; u <= t; ++u)
-                            at[u] = Ew[tri(j0 + min(t, pw - 1), j0 + min(u, pw - 1))];
-#pragma unroll
-                        for (int u = 0; u <= t; ++u)
-                            at[u] = t < pw ? at[u] : (u == t ? 1.0 : 0.0);
-                        // row t of the block against the rows above it (left-looking)
-#pragma unroll
-                        for (int u = 0; u < t; ++u) {
-                            double x = at[u];
-#pragma unroll
-                            for (int s2 = 0; s2 < u; ++s2) x = fma(-Lm[t][s2] * Dv[s2], Lm[u][s2], x);
-                            Lm[t][u] = x * Di[u];
-                        }
-                        double d = at[t];
-#pragma unroll
-                        for (int s2 = 0; s2 < t; ++s2) d = fma(-Lm[t][s2] * Dv[s2], Lm[t][s2], d);
-                        Dv[t] = d;
-                        Di[t] = d != 0.0 ? pivot_rcp(d) : 0.0;   // exact-zero pivot: column skipped
-                    }
-#pragma unroll
-                    for (int t = 0; t < kLdlPw; ++t)
-                        if (t < pw) minpiv = fmin(minpiv, Dv[t]);
-                    if (lane >= j0 && lane < nrows) {
-                        if (lane < j0 + pw) {   // a row of the block: L and D from the factor
-#pragma unroll
-                            for (int t = 0; t < kLdlPw; ++t)
-                                if (lane - j0 == t) {
-#pragma unroll
-                                    for (int u = 0; u < t; ++u) Ew[tri(lane, j0 + u)] = Lm[t][u];
-                                    Ew[tri(lane, lane)] = Dv[t];
-                                }
-                        } else {   // a row below: z L11^T = a_i, l_i = z / D
-                            double z[kLdlPw];
-#pragma unroll
-                            for (int t = 0; t < kLdlPw; ++t) z[t] = Ew[tri(lane, j0 + min(t, pw - 1))];
-#pragma unroll
-                            for (int t = 0; t < kLdlPw; ++t) {
-                                z[t] = t < pw ? z[t] : 0.0;
-#pragma unroll
-                                for (int s2 = 0; s2 < t; ++s2) z[t] = fma(-z[s2], Lm[t][s2], z[t]);
-                            }
-#pragma unroll
-                            for (int t = 0; t < kLdlPw; ++t)
-                                if (t < pw) Ew[tri(lane, j0 + t)] = z[t] * Di[t];
-                        }
-                    }
+                    double Dv[kLdlPw];
+                    ldl_panel(Ew, lane, nrows, j0, pw, true, Dv, minpiv);
                     WAVE_SYNC();
-                    const int r0 = j0 + pw;
-                    if (r0 < n) {
-                        const int ntr = (nrows - r0 + 15) >> 4, ntc = (n - r0 + 15) >> 4;
-                        // MFMA step s takes the panel's columns 4s .. 4s + 3 (lane group lk)
+                    if (j0 + pw < n) {
                         double dk[kLdlPw / 4];
                         int kc[kLdlPw / 4];
 #pragma unroll
@@ -1351,53 +1700,7 @@ __device__ __forceinline__ void rating_user(const PredArgs<T> a, uint32_t uo, do
                             dk[s4] = dsel;
                             kc[s4] = j0 + min(4 * s4 + lk, pw - 1);
                         }
-                        for (int ti = 0; ti < ntr; ++ti) {
-                            const int arow = r0 + 16 * ti + li;
-                            double aop[kLdlPw / 4];
-#pragma unroll
-                            for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
-                                const double av = Ew[tri(min(arow, nrows - 1), kc[s4])];
-                                aop[s4] = (arow < nrows && 4 * s4 + lk < pw) ? -av * dk[s4] : 0.0;
-                            }
-                            const int tmax = min(ti, ntc - 1);
-                            // two tiles of the row at a time: loads, then MFMAs, then stores
-                            for (int tq0 = 0; tq0 <= tmax; tq0 += 2) {
-                                f64x4 acc[2];
-                                double bop[2][kLdlPw / 4];
-#pragma unroll
-                                for (int x = 0; x < 2; ++x) {
-                                    const int col = r0 + 16 * (tq0 + x) + li;
-#pragma unroll
-                                    for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
-                                        const double bv = Ew[tri(min(col, n - 1), kc[s4])];
-                                        bop[x][s4] = (col < n && 4 * s4 + lk < pw) ? bv : 0.0;
-                                    }
-#pragma unroll
-                                    for (int q = 0; q < 4; ++q) {
-                                        const int row = r0 + 16 * ti + lk + 4 * q;
-                                        const int rc = min(row, nrows - 1);
-                                        const double v = Ew[tri(rc, min(col, rc))];
-                                        acc[x][q] = (tq0 + x <= tmax && row < nrows && col < n && col <= row) ? v : 0.0;
-                                    }
-                                }
-#pragma unroll
-                                for (int s4 = 0; s4 < kLdlPw / 4; ++s4) {
-                                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s4], bop[0][s4], acc[0], 0, 0, 0);
-                                    if (tq0 + 1 <= tmax)
-                                        acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[s4], bop[1][s4], acc[1], 0, 0, 0);
-                                }
-#pragma unroll
-                                for (int x = 0; x < 2; ++x) {
-                                    const int col = r0 + 16 * (tq0 + x) + li;
-#pragma unroll
-                                    for (int q = 0; q < 4; ++q) {
-                                        const int row = r0 + 16 * ti + lk + 4 * q;
-                                        if (tq0 + x <= tmax && row < nrows && col < n && col <= row)
-                                            Ew[tri(row, col)] = acc[x][q];
-                                    }
-                                }
-                            }
-                        }
+                        ldl_trailing(Ew, n, nrows, j0, pw, dk, kc);
                     }
                     WAVE_SYNC();
                 }
@@ -1421,12 +1724,12 @@ __device__ __forceinline__ void rating_user(const PredArgs<T> a, uint32_t uo, do
                     a.kk[base + r] = c;
                     if (a.pred) a.pred[base + r] = pred;
                 }
-                if (a.phase_cycles) {   // per nc class: cycles, count (wave-uniform)
+                if (a.phase_cycles) {   // per class of n: cycles, count (wave-uniform)
                     const unsigned long long dt = __builtin_amdgcn_s_memtime() - rt0;
-                    if (nc <= 4) {
+                    if (n <= kQuadNMax) {
                         wacc[3] += dt;
                         wacc[6] += 1;
-                    } else if (nc <= 16) {
+                    } else if (n <= kPairNMax) {
                         wacc[4] += dt;
                         wacc[7] += 1;
                     } else {
@@ -1434,6 +1737,11 @@ __device__ __forceinline__ void rating_user(const PredArgs<T> a, uint32_t uo, do
                     }
                 }
             }
+            // pairs, then quads; the last group of a list may be short
+            for (int i0 = claim(&s_cnt[9], 2); i0 < n_pair; i0 = claim(&s_cnt[9], 2))
+                packed(std::integral_constant<int, 2>{}, s_keep + i0, min(2, n_pair - i0));
+            for (int i0 = claim(&s_cnt[10], 4); i0 < n_quad; i0 = claim(&s_cnt[10], 4))
+                packed(std::integral_constant<int, 4>{}, s_nconn + i0, min(4, n_quad - i0));
             if (a.phase_cycles) {
                 wacc[2] += __builtin_amdgcn_s_memtime() - fw0;
                 if (lane == 0)
@@ -1595,7 +1903,6 @@ inline uint32_t pred_chunk() {
     }();
     return c;
 }
-inline int fast_tri(int n) { return (n + 2) * (n + 3) / 2; }
 inline SlotOff slot_layout(int lmax) {
     SlotOff so{};
     size_t o = 0;
@@ -1678,6 +1985,15 @@ int setup_bucket(cf_ctx* ctx, PredArgs<T>& args, int lmax, size_t& rating_lds) {
     while (nmax > 8 && sizeof(double) * (size_t)(kWaves * per_wave(nmax)) + lds_fixed > kRatingLds) --nmax;
     args.nmax = nmax;
     args.ew = per_wave(nmax);
+    // Lane packing needs room for four quad or two pair systems per wave.  nmax and the blocks
+    // per CU are never traded for it: a bucket where it does not fit keeps one rating per wave.
+    if (ctx->pred_pack < 0) {   // CF_PRED_PACK: 0 off, default on
+        const char* e = std::getenv("CF_PRED_PACK");
+        ctx->pred_pack = e && e[0] == '0' ? 0 : 1;
+    }
+    const int ew_pack = std::max(pack_elems(4, kQuadNMax, lmax), pack_elems(2, kPairNMax, lmax));
+    args.pack = ctx->pred_pack && sizeof(double) * (size_t)(kWaves * std::max(args.ew, ew_pack)) + lds_fixed <= kRatingLds;
+    if (args.pack) args.ew = std::max(args.ew, ew_pack);
     args.big_lds = sizeof(double) * (size_t)std::max(big, kWaves * args.ew) + lds_fixed <= kRatingLds;
     args.a_elems = std::max({args.big_lds ? big : 0, kWaves * args.ew, 2 * lmax});
     args.so = slot_layout(lmax);
@@ -2094,6 +2410,13 @@ template int cf_launch_predict<double>(cf_ctx*, const cf_plan*, const uint64_t*,
                                        const float*, const int32_t*, const double*,
                                        const uint64_t*, const double*, const double*, int, float*,
                                        int32_t*, double*, const uint8_t*, hipStream_t);
+
+extern "C" int cf_set_pred_pack(cf_ctx* ctx, int mode) {
+    if (!ctx) return CF_EINVAL;
+    if (mode != 0 && mode != 1) return CF_EINVAL;
+    ctx->pred_pack = mode;
+    return CF_OK;
+}
 
 // The fast path's largest system (rows min(nc, d)) in a bucket of Gram bound lmax: the nmax
 // setup_bucket derives from the LDS budget.  Ratings with a larger system take the block-wide

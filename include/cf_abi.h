@@ -99,6 +99,11 @@ int cf_set_eigen_refine(cf_ctx* ctx, int enable, float stop_rel, float delta);
  * CF_EIGEN_SPLIT sets the same.  Same algorithm, same outputs up to the rotation order inside odd
  * segments.  Same call site as cf_eigen_run. */
 int cf_set_eigen_split(cf_ctx* ctx, int enable);
+/* Predictor fast path, lane packing: mode 1 (default) runs the per-rating systems of
+ * n = min(nc, d) <= 14 rows four to a wave and those of 15..30 rows two to a wave; mode 0 gives every
+ * rating a wave of its own.  Outputs are bit-identical either way; env CF_PRED_PACK sets the same.
+ * Applies to cf_predict_run*, cf_predict_precomp and cf_step_run. */
+int cf_set_pred_pack(cf_ctx* ctx, int mode);
 /* Host only (no device): builds and verifies the split layout's sweep schedule for k columns in
  * LDS bucket emax (every pair of columns meets once per sweep, no two lane groups touch one LDS
  * slot in a level change, register groups and slots within capacity).  Returns CF_OK and the
@@ -140,8 +145,8 @@ int cf_debug_tri(cf_ctx* ctx, int enable, uint64_t* out8);
  * cycles of the per-user Gbar GEMM and of the block-wide K path (a subset of the
  * block-wide cycles).  out16[8..15], summed over every wave: fast-path cycles in
  * {P/PG/PH gathers and border rows, LDL^T of K, the whole fast phase}, the cycles of
- * completed fast-path ratings with nc <= 4, 5..16 and > 16, and the counts of the first
- * two classes. */
+ * completed fast-path ratings whose system has n = min(nc, d) <= 14, 15..30 and > 30 rows
+ * (a packed group's cycles once, under its class), and the counts of the first two classes. */
 int cf_debug_phases(cf_ctx* ctx, int enable, uint64_t* out16);
 /* The predictor's fast-path system bound (rows min(nc, d)) in a k-bucket whose
  * Gram bound is lmax = 16 ceil(k / 16): ratings above it take the block-wide path.  -1 if

@@ -1,5 +1,7 @@
 """Diagnostics on the C4 workload (knn2 graph, 50k items): predictor phase cycles, the nc /
-c / lim distribution of the ratings, and stage times of a user range.
+c / lim distribution of the ratings, and stage times of a user range.  The predictor figures are
+taken with lane packing off and on (cf_set_pred_pack) in this one process, and the histogram of
+the system size n = min(nc, d) is printed by mode in the packing classes.
 usage: probe_c4.py [users=125000] [first=0]   (PROBE_CFG=c2 for the C2 workload)"""
 import os
 import sys
@@ -45,7 +47,7 @@ def pred():
                      CF_SIGS_COMPAT, d["mse"], d["kk"])
 
 
-for f, name in ((eig, "eigen"), (pred, "predict")):
+def timed(f, name):
     f()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -55,26 +57,40 @@ for f, name in ((eig, "eigen"), (pred, "predict")):
     e1.synchronize()
     print(f"{name}: {e0.elapsed_time(e1):.1f} ms for {users} users / {n} ratings", flush=True)
 
+
+timed(eig, "eigen")
+saved = {}
+for pack in (0, 1, 0, 1):
+    ctx.set_pred_pack(pack)
+    timed(pred, f"predict pack={pack}")
+    out = dict(mse=d["mse"].cpu().numpy(), kk=d["kk"].cpu().numpy())
+    if pack in saved:
+        continue
+    saved[pack] = out
+    ctx.debug_phases(True)
+    pred()
+    torch.cuda.synchronize()
+    ph = ctx.debug_phases(True, read=True)
+    ctx.debug_phases(False)
+    cyc = {k_: ph[k_] for k_ in ("setup", "basis", "fast", "dense")}
+    tot = sum(cyc.values())
+    print(f"pack={pack} phase share of block cycles:", {k_: f"{v / tot * 100:.1f}%" for k_, v in cyc.items()},
+          "| fast ratings", ph["n_fast"], "block-wide ratings", ph["n_dense"],
+          "| wide-K share of block-wide cycles", f"{ph['wide'] / max(ph['dense'], 1) * 100:.1f}%",
+          "| gram share of setup+basis", f"{ph['gram'] / max(ph['setup'] + ph['basis'], 1) * 100:.1f}%")
+    wf = max(ph["w_fast"], 1)
+    print(f"pack={pack} fast path wave-cycles: gathers+border", f"{ph['w_gather'] / wf * 100:.1f}%", "LDL^T",
+          f"{ph['w_ldlt'] / wf * 100:.1f}%", "per fast rating", wf / max(ph["n_fast"], 1))
+    csum = max(ph["cyc_n14"] + ph["cyc_n30"] + ph["cyc_nbig"], 1)
+    print(f"pack={pack} solved ratings by n = min(nc, d): n<=14", ph["n_n14"], "cyc/rating", ph["cyc_n14"] / max(ph["n_n14"], 1),
+          f"share {ph['cyc_n14'] / csum * 100:.1f}%", "| 15..30", ph["n_n30"], ph["cyc_n30"] / max(ph["n_n30"], 1),
+          f"share {ph['cyc_n30'] / csum * 100:.1f}%", "| >30 cycles share", f"{ph['cyc_nbig'] / csum * 100:.1f}%")
+    print(f"pack={pack} block cycles per user", tot / users, "per rating", tot / n, flush=True)
+same = all(np.array_equal(saved[0][k_].view(np.uint32), saved[1][k_].view(np.uint32)) for k_ in ("mse", "kk"))
+print("pack on == pack off, every mse and kk bit:", same, f"({n} ratings)")
+
 if os.environ.get("PROBE_SAVE"):   # outputs of the timed configuration, for A/B equality checks
     np.savez(os.environ["PROBE_SAVE"], mse=d["mse"].cpu().numpy(), kk=d["kk"].cpu().numpy())
-ctx.debug_phases(True)
-pred()
-torch.cuda.synchronize()
-ph = ctx.debug_phases(True, read=True)
-ctx.debug_phases(False)
-cyc = {k_: ph[k_] for k_ in ("setup", "basis", "fast", "dense")}
-tot = sum(cyc.values())
-print("phase share of block cycles:", {k_: f"{v / tot * 100:.1f}%" for k_, v in cyc.items()},
-      "| fast ratings", ph["n_fast"], "block-wide ratings", ph["n_dense"],
-      "| wide-K share of block-wide cycles", f"{ph['wide'] / max(ph['dense'], 1) * 100:.1f}%",
-      "| gram share of setup+basis", f"{ph['gram'] / max(ph['setup'] + ph['basis'], 1) * 100:.1f}%")
-wf = max(ph["w_fast"], 1)
-print("fast path wave-cycles: gathers+border", f"{ph['w_gather'] / wf * 100:.1f}%", "LDL^T",
-      f"{ph['w_ldlt'] / wf * 100:.1f}%", "per fast rating", wf / max(ph["n_fast"], 1))
-nbig = max(ph["n_fast"] - ph["n_nc4"] - ph["n_nc16"], 1)
-print("fast ratings: nc<=4", ph["n_nc4"], "cyc", ph["cyc_nc4"] / max(ph["n_nc4"], 1), "| 5..16", ph["n_nc16"],
-      ph["cyc_nc16"] / max(ph["n_nc16"], 1), "| >16", nbig, ph["cyc_ncbig"] / nbig)
-print("block cycles per user", tot / users, "per rating", tot / n)
 
 m = d["m"].cpu().numpy()
 kk = d["kk"].cpu().numpy()
@@ -98,5 +114,11 @@ print("lim mean", ls.mean(), "| c < lim (rank-deficient)", (cs < ls).mean(), "| 
       "| wide & c>=lim", ((ns > 62) & (cs >= ls)).mean())
 print("wide ratings: c mean", cs[ns > 62].mean() if (ns > 62).any() else 0, "lim mean", ls[ns > 62].mean() if (ns > 62).any() else 0,
       "nc mean", ns[ns > 62].mean() if (ns > 62).any() else 0)
+ds = kr[sel] - ls
+nsys = np.minimum(ns, ds)
+for name, msk in (("K-mode (nc <= d)", ns <= ds), ("G-mode (nc > d)", ns > ds)):
+    solved = msk & (ns > 1)   # nc = 1 is closed form in the basis kernel
+    print(f"n = min(nc, d) of {int(sel.sum())} ratings, {name}: nc=1", int((msk & (ns == 1)).sum()), "| n<=14", int((solved & (nsys <= 14)).sum()),
+          "| 15..30", int((solved & (nsys > 14) & (nsys <= 30)).sum()), "| >30", int((solved & (nsys > 30)).sum()))
 h = np.histogram(nc, bins=[0, 1, 5, 9, 17, 33, 63, 96, 128, 200])[0]
 print("nc histogram [0,1,5,9,17,33,63,96,128,200):", h.tolist())
