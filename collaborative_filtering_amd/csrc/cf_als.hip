@@ -18,35 +18,19 @@
 // nnz (8 D + 8) bytes (one D-long fp64 row, the neighbour id and the rating per edge) and does
 // nnz D (D + 1) flops: bound by the row gathers, not by the fp64 units.
 //
-// Work is shaped by the vertex's TRAIN degree, with cuts that are constants of cf_mf_common.h:
-//   low   deg <= kLowMax           one wave per vertex, kWaves vertices per workgroup
-//   mid   kLowMax < deg <= kSeg    one workgroup per vertex: its waves take contiguous quarters
-//                                  of the list, the partial (A, b) are summed in wave order in LDS
-//   high  deg > kSeg               the list is cut into segments of kSeg edges; one workgroup per
-//                                  segment (as mid) writes its partial to an HBM workspace, and a
-//                                  wave per vertex sums the partials in segment order and solves
-// Determinism rule: the class, the split points and every summation order of a vertex depend on
-// its own degree only -- never on the launch, the active list or other vertices -- and there is
-// no floating-point atomic, so a vertex's new factor is the same bits whichever other vertices
-// are active and however often a fit is repeated.  (The Gram kernels below implement the rule
-// for ALS; SGD and SVD++ share one implementation of it, cf_mf_reduce.h.)
-//
-// The Gram of one wave and the solve are in cf_als_gram.h (shared with cf_ials.hip): D is padded
-// to DP = 8 / 16 / 32 / 64 and lane l owns the TS x TS block (TS = DP / 8) at block row l >> 3,
-// block column l & 7 of A, in registers; neighbour rows are staged kBatch at a time (coalesced)
-// in wave-private LDS and every lane reads its 2 TS values per neighbour from there.  Each
-// element is one fma chain in CSR order.
-// The solve is an unpivoted LDL^T of the packed lower triangle (= the upper triangle the
-// reference factors, als.cpp:330) with b carried as a border row (the layout of cf_ldlt.hpp),
-// done by one wave in LDS for D <= 64.  An exactly zero pivot is skipped as cf_ldlt.hpp
-// documents; pivots <= 0 (or NaN) are counted (n_not_pd).
+// Work is shaped by the vertex's TRAIN degree: the three classes (low / mid / high), the
+// determinism rule they carry and the update kernels are in cf_als_update.h, shared with
+// cf_ials.hip; this file gives them the policy AlsOp.  The Gram of one wave and the one-wave
+// unpivoted LDL^T solve (the upper triangle the reference factors, als.cpp:330; an exactly zero
+// pivot is skipped as cf_ldlt.hpp documents, pivots <= 0 or NaN are counted in n_not_pd) are in
+// cf_als_gram.h.
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
-#include "cf_als_gram.h"
+#include "cf_als_update.h"
 #include "cf_internal.h"
 #include "cf_mf_common.h"
 
@@ -67,115 +51,38 @@ struct AlsSide {
     uint8_t* active;       // active in the current superstep of this side
 };
 
-// apply's tail for vertex v with the system in S: solve, residual, store.  One wave.
-__device__ inline void wave_apply(double* S, int D, const AlsSide& s, uint32_t v, unsigned long long* not_pd,
-                                  int lane) {
-    const int bad = wave_ldlt_solve(S, D, s.reg[v], lane);
-    double* Fv = s.F + (size_t)v * D;
-    double diff = 0.0;
-    for (int d = lane; d < D; d += 64) {
-        const double x = S[tri(D, d)];
-        diff += fabs(x - Fv[d]);
-        Fv[d] = x;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) diff += __shfl_xor(diff, o);
-    if (lane == 0) {
-        s.resid[v] = (float)(diff / (double)D);
-        s.nupd[v] += 1;
-        if (bad) atomicAdd(not_pd, (unsigned long long)bad);   // integer counter
-    }
-}
-
-// low class: one wave per vertex.
-template <int DP>
-__global__ __launch_bounds__(kAT) void als_low_kernel(AlsSide s, const double* __restrict__ Fo, int D,
-                                                     const uint32_t* __restrict__ list, uint32_t count,
-                                                     unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[kWaves * low_region<DP>()];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count) return;   // whole waves leave; no block barrier below
-    const uint32_t v = list[j];
-    const uint64_t p0 = s.off[v], p1 = s.off[v + 1];
-    if (p1 == p0) {   // no TRAIN edge (als.cpp:319)
+// The policy of cf_als_update.h: the unweighted edge, and apply's tail for vertex v.
+struct AlsOp {
+    static constexpr bool kWeighted = false;
+    AlsSide s;
+    __device__ const float* edge_obs() const { return s.obs; }
+    __device__ const float* edge_pref() const { return nullptr; }
+    // no TRAIN edge (als.cpp:319)
+    __device__ void no_edges(uint32_t v, int, int lane) const {
         if (lane == 0) {
             s.resid[v] = 0.0f;
             s.nupd[v] += 1;
         }
-        return;
     }
-    double* R = lds + wave * low_region<DP>();
-    Gram<DP> g;
-    g.clear();
-    gram_accumulate<DP, false>(g, R, Fo, D, s.nbr, s.obs, nullptr, p0, p1, lane);
-    gram_to_system<DP, false>(g, R, D, lane);
-    WAVE_SYNC();
-    wave_apply(R, D, s, v, not_pd, lane);
-}
-
-// mid class (SEGMENT = false): one workgroup per vertex, solved here.  high class (SEGMENT =
-// true): one workgroup per (vertex, segment); the partial system goes to workspace slot
-// blockIdx.x (sys_len(D) doubles per slot).
-template <int DP, bool SEGMENT>
-__global__ __launch_bounds__(kAT) void als_group_kernel(AlsSide s, const double* __restrict__ Fo, int D,
-                                                       const uint32_t* __restrict__ list,
-                                                       const uint32_t* __restrict__ seg_index, double* ws,
-                                                       unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[mid_region<DP>()];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t v = list[blockIdx.x];
-    uint64_t p0 = s.off[v];
-    uint64_t len = s.off[v + 1] - p0;
-    if (SEGMENT) {
-        const uint64_t first = (uint64_t)seg_index[blockIdx.x] * kSeg;
-        p0 += first;
-        len = len - first < (uint64_t)kSeg ? len - first : (uint64_t)kSeg;
-    }
-    const uint64_t chunk = (len + kWaves - 1) / kWaves;
-    const uint64_t b = std::min(len, wave * chunk), e = std::min(len, (wave + 1) * chunk);
-    Gram<DP> g;
-    g.clear();
-    gram_accumulate<DP, false>(g, lds + wave * kBatch * DP, Fo, D, s.nbr, s.obs, nullptr, p0 + b, p0 + e, lane);
-    __syncthreads();   // the staging rows are dead: the system takes their place
-    if (wave == 0) gram_to_system<DP, false>(g, lds, D, lane);
-    __syncthreads();
+    // with the system in S: solve, residual, store
+    __device__ void apply(double* S, int D, uint32_t v, unsigned long long* not_pd, int lane) const {
+        const int bad = wave_ldlt_solve(S, D, s.reg[v], lane);
+        double* Fv = s.F + (size_t)v * D;
+        double diff = 0.0;
+        for (int d = lane; d < D; d += 64) {
+            const double x = S[tri(D, d)];
+            diff += fabs(x - Fv[d]);
+            Fv[d] = x;
+        }
 #pragma unroll
-    for (int w = 1; w < kWaves; ++w) {   // partials summed in wave order
-        if (wave == w) gram_to_system<DP, true>(g, lds, D, lane);
-        __syncthreads();
+        for (int o = 32; o >= 1; o >>= 1) diff += __shfl_xor(diff, o);
+        if (lane == 0) {
+            s.resid[v] = (float)(diff / (double)D);
+            s.nupd[v] += 1;
+            if (bad) atomicAdd(not_pd, (unsigned long long)bad);   // integer counter
+        }
     }
-    if (SEGMENT) {
-        double* slot = ws + (size_t)blockIdx.x * sys_len(D);
-        for (int t = threadIdx.x; t < sys_len(D); t += kAT) slot[t] = lds[t];
-    } else if (wave == 0) {
-        wave_apply(lds, D, s, v, not_pd, lane);
-    }
-}
-
-// high class, second pass: one wave per vertex sums its segments' partials in segment order.
-template <int DP>
-__global__ __launch_bounds__(kAT) void als_finish_kernel(AlsSide s, int D, const uint32_t* __restrict__ list,
-                                                        const uint32_t* __restrict__ base, uint32_t count,
-                                                        const double* __restrict__ ws, unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[kWaves * ((sys_len(DP) + 1) & ~1)];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count) return;
-    const uint32_t v = list[j];
-    const uint64_t deg = s.off[v + 1] - s.off[v];
-    const uint32_t nseg = (uint32_t)((deg + kSeg - 1) / kSeg);
-    double* S = lds + wave * ((sys_len(DP) + 1) & ~1);
-    const int n = sys_len(D);
-    const double* slot = ws + (size_t)base[j] * n;
-    for (int t = lane; t < n; t += 64) {
-        double acc = slot[t];
-        for (uint32_t q = 1; q < nseg; ++q) acc += slot[(size_t)q * n + t];
-        S[t] = acc;
-    }
-    WAVE_SYNC();
-    wave_apply(S, D, s, v, not_pd, lane);
-}
+};
 
 // scatter (als.cpp:343-357) over every edge of the side just updated; edges of inactive
 // vertices leave at once.  The flag stores are plain and all write the same value.
@@ -220,24 +127,6 @@ void carve_fit(Carver& c, FitLayout& f, uint32_t n_users, uint32_t n_items, uint
     f.ws = c.take<double>((size_t)seg_cap * sys_len(D));
     f.not_pd = c.take<unsigned long long>(1);
     f.seg_cap = (uint32_t)seg_cap;
-}
-
-template <int DP>
-void launch_update(const FitLayout& f, int k, int D, const uint32_t rec[4], hipStream_t st) {
-    const AlsSide& s = f.side[k];
-    const double* Fo = f.side[1 - k].F;
-    if (rec[0])
-        hipLaunchKernelGGL(als_low_kernel<DP>, dim3((rec[0] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, Fo, D,
-                           f.lists.low, rec[0], f.not_pd);
-    if (rec[1])
-        hipLaunchKernelGGL((als_group_kernel<DP, false>), dim3(rec[1]), dim3(kAT), 0, st, s, Fo, D, f.lists.mid,
-                           (const uint32_t*)nullptr, (double*)nullptr, f.not_pd);
-    if (rec[2]) {
-        hipLaunchKernelGGL((als_group_kernel<DP, true>), dim3(rec[3]), dim3(kAT), 0, st, s, Fo, D, f.lists.seg_vertex,
-                           f.lists.seg_index, f.ws, f.not_pd);
-        hipLaunchKernelGGL(als_finish_kernel<DP>, dim3((rec[2] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, D,
-                           f.lists.high, f.lists.high_base, rec[2], f.ws, f.not_pd);
-    }
 }
 
 }  // namespace
@@ -291,7 +180,6 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     }
     CF_HIP_CHECK(ctx, hipMemset(f.not_pd, 0, sizeof(unsigned long long)));
 
-    const int DP = D <= 8 ? 8 : (D <= 16 ? 16 : (D <= 32 ? 32 : 64));
     if ((nnz * kG + kAT - 1) / kAT > 0x7fffffffull) return cf_set_error(ctx, CF_ERANGE, "cf_als_fit: too many edges");
     const unsigned scatter_blocks = (unsigned)((nnz * kG + kAT - 1) / kAT);
     uint32_t supersteps = 0;
@@ -313,12 +201,7 @@ extern "C" int cf_als_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         if (max_supersteps && supersteps >= max_supersteps) break;
         if (rec[3] > f.seg_cap) return cf_set_error(ctx, CF_EHIP, "cf_als_fit: segment list overflow");
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        switch (DP) {
-            case 8: launch_update<8>(f, k, (int)D, rec, st); break;
-            case 16: launch_update<16>(f, k, (int)D, rec, st); break;
-            case 32: launch_update<32>(f, k, (int)D, rec, st); break;
-            default: launch_update<64>(f, k, (int)D, rec, st); break;
-        }
+        launch_update(AlsOp{f.side[k]}, f.side[1 - k].F, (int)D, f.lists, rec, f.ws, f.not_pd, st);
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
         if (nnz && n[1 - k])
             hipLaunchKernelGGL(als_scatter_kernel, dim3(scatter_blocks), dim3(kAT), 0, st, f.side[k], nnz,

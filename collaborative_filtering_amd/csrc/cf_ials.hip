@@ -18,9 +18,8 @@
 // every run, and a slice's partial depends on its own rows only.  Reads n 8 D bytes once and does
 // n D^2 fma.
 //
-// Per-vertex update, in ALS's three degree classes (cuts kLowMax / kSeg of cf_mf_common.h; low =
-// one wave per vertex, mid = one workgroup per vertex, high = segments of kSeg edges with partials
-// in HBM and a finishing wave per vertex).  ORDER OF THE SYSTEM, the same in all three classes:
+// Per-vertex update, in the three degree classes of cf_als_update.h (shared with cf_als.hip; this
+// file gives its kernels the policy IalsOp).  ORDER OF THE SYSTEM, the same in all three classes:
 //   1. the edge sums start from zero: A_e = sum (c - 1) x x^T, b = sum (c p) x, each element one
 //      fma chain in CSR order within a wave's edge range (gram_accumulate<DP, true>); the ranges
 //      are summed in wave order, then (high) in segment order
@@ -44,9 +43,8 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 
-#include "cf_als_gram.h"
+#include "cf_als_update.h"
 #include "cf_internal.h"
 #include "cf_mf_common.h"
 
@@ -152,106 +150,26 @@ __global__ __launch_bounds__(kAT) void ials_gram_sum_kernel(const double* __rest
 
 // ---- per-vertex update -----------------------------------------------------------------------
 
-// The tail of an update for vertex v with the edge sums in S: steps 2-4 of the header.  One wave.
-__device__ inline void ials_wave_apply(double* S, int D, const double* __restrict__ Gp, const IalsSide& s, uint32_t v,
-                                       unsigned long long* not_pd, int lane) {
-    for (int t = lane; t < D * (D + 1) / 2; t += 64) S[t] += Gp[t];
-    WAVE_SYNC();
-    const int bad = wave_ldlt_solve(S, D, s.reg[v], lane);
-    double* Fv = s.F + (size_t)v * D;
-    for (int d = lane; d < D; d += 64) Fv[d] = S[tri(D, d)];
-    if (lane == 0 && bad) atomicAdd(not_pd, (unsigned long long)bad);   // integer counter
-}
-
-// low class: one wave per vertex.
-template <int DP>
-__global__ __launch_bounds__(kAT) void ials_low_kernel(IalsSide s, const double* __restrict__ Fo,
-                                                      const double* __restrict__ Gp, int D,
-                                                      const uint32_t* __restrict__ list, uint32_t count,
-                                                      unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[kWaves * low_region<DP>()];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count) return;   // whole waves leave; no block barrier below
-    const uint32_t v = list[j];
-    const uint64_t p0 = s.off[v], p1 = s.off[v + 1];
-    if (p1 == p0) {   // b = 0: the minimiser is the zero vector
+// The policy of cf_als_update.h: the weighted edge, and steps 2-4 of the header as the tail.
+struct IalsOp {
+    static constexpr bool kWeighted = true;
+    IalsSide s;
+    const double* Gp;   // packed lower triangle of the other side's Gram
+    __device__ const float* edge_obs() const { return s.conf; }
+    __device__ const float* edge_pref() const { return s.pref; }
+    // b = 0: the minimiser is the zero vector
+    __device__ void no_edges(uint32_t v, int D, int lane) const {
         for (int d = lane; d < D; d += 64) s.F[(size_t)v * D + d] = 0.0;
-        return;
     }
-    double* R = lds + wave * low_region<DP>();
-    Gram<DP> g;
-    g.clear();
-    gram_accumulate<DP, true>(g, R, Fo, D, s.nbr, s.conf, s.pref, p0, p1, lane);
-    gram_to_system<DP, false>(g, R, D, lane);
-    WAVE_SYNC();
-    ials_wave_apply(R, D, Gp, s, v, not_pd, lane);
-}
-
-// mid class (SEGMENT = false): one workgroup per vertex, solved here.  high class (SEGMENT =
-// true): one workgroup per (vertex, segment); the partial edge sums go to workspace slot
-// blockIdx.x (sys_len(D) doubles per slot).
-template <int DP, bool SEGMENT>
-__global__ __launch_bounds__(kAT) void ials_group_kernel(IalsSide s, const double* __restrict__ Fo,
-                                                        const double* __restrict__ Gp, int D,
-                                                        const uint32_t* __restrict__ list,
-                                                        const uint32_t* __restrict__ seg_index, double* ws,
-                                                        unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[mid_region<DP>()];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t v = list[blockIdx.x];
-    uint64_t p0 = s.off[v];
-    uint64_t len = s.off[v + 1] - p0;
-    if (SEGMENT) {
-        const uint64_t first = (uint64_t)seg_index[blockIdx.x] * kSeg;
-        p0 += first;
-        len = len - first < (uint64_t)kSeg ? len - first : (uint64_t)kSeg;
+    __device__ void apply(double* S, int D, uint32_t v, unsigned long long* not_pd, int lane) const {
+        for (int t = lane; t < D * (D + 1) / 2; t += 64) S[t] += Gp[t];
+        WAVE_SYNC();
+        const int bad = wave_ldlt_solve(S, D, s.reg[v], lane);
+        double* Fv = s.F + (size_t)v * D;
+        for (int d = lane; d < D; d += 64) Fv[d] = S[tri(D, d)];
+        if (lane == 0 && bad) atomicAdd(not_pd, (unsigned long long)bad);   // integer counter
     }
-    const uint64_t chunk = (len + kWaves - 1) / kWaves;
-    const uint64_t b = std::min(len, wave * chunk), e = std::min(len, (wave + 1) * chunk);
-    Gram<DP> g;
-    g.clear();
-    gram_accumulate<DP, true>(g, lds + wave * kBatch * DP, Fo, D, s.nbr, s.conf, s.pref, p0 + b, p0 + e, lane);
-    __syncthreads();   // the staging rows are dead: the system takes their place
-    if (wave == 0) gram_to_system<DP, false>(g, lds, D, lane);
-    __syncthreads();
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) {   // partials summed in wave order
-        if (wave == w) gram_to_system<DP, true>(g, lds, D, lane);
-        __syncthreads();
-    }
-    if (SEGMENT) {
-        double* slot = ws + (size_t)blockIdx.x * sys_len(D);
-        for (int t = threadIdx.x; t < sys_len(D); t += kAT) slot[t] = lds[t];
-    } else if (wave == 0) {
-        ials_wave_apply(lds, D, Gp, s, v, not_pd, lane);
-    }
-}
-
-// high class, second pass: one wave per vertex sums its segments' partials in segment order.
-template <int DP>
-__global__ __launch_bounds__(kAT) void ials_finish_kernel(IalsSide s, const double* __restrict__ Gp, int D,
-                                                         const uint32_t* __restrict__ list,
-                                                         const uint32_t* __restrict__ base, uint32_t count,
-                                                         const double* __restrict__ ws, unsigned long long* not_pd) {
-    __shared__ __attribute__((aligned(16))) double lds[kWaves * ((sys_len(DP) + 1) & ~1)];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t j = blockIdx.x * kWaves + wave;
-    if (j >= count) return;
-    const uint32_t v = list[j];
-    const uint64_t deg = s.off[v + 1] - s.off[v];
-    const uint32_t nseg = (uint32_t)((deg + kSeg - 1) / kSeg);
-    double* S = lds + wave * ((sys_len(DP) + 1) & ~1);
-    const int n = sys_len(D);
-    const double* slot = ws + (size_t)base[j] * n;
-    for (int t = lane; t < n; t += 64) {
-        double acc = slot[t];
-        for (uint32_t q = 1; q < nseg; ++q) acc += slot[(size_t)q * n + t];
-        S[t] = acc;
-    }
-    WAVE_SYNC();
-    ials_wave_apply(S, D, Gp, s, v, not_pd, lane);
-}
+};
 
 // ---- loss --------------------------------------------------------------------------------
 
@@ -315,14 +233,6 @@ __global__ void ials_loss_combine_kernel(const double* __restrict__ four, double
 // ---- host ---------------------------------------------------------------------------------
 
 inline uint32_t gram_slices(uint32_t n) { return (uint32_t)(((uint64_t)n + kGramRows - 1) / kGramRows); }
-
-template <class Fn>
-void dispatch_dp(int D, Fn fn) {
-    if (D <= 8) fn(std::integral_constant<int, 8>{});
-    else if (D <= 16) fn(std::integral_constant<int, 16>{});
-    else if (D <= 32) fn(std::integral_constant<int, 32>{});
-    else fn(std::integral_constant<int, 64>{});
-}
 
 // G (and, where Gp is not NULL, its packed lower triangle) of the n x D device matrix F.
 void launch_gram(const double* F, uint32_t n, int D, double* partial, double* G, double* Gp, hipStream_t st) {
@@ -429,34 +339,9 @@ int upload_ials(cf_ctx* ctx, const IalsLayout& f, const IalsArgs& a, const doubl
         CF_HIP_CHECK(ctx, hipMemset(s.flag, 1, n));
         CF_HIP_CHECK(ctx, hipMemset(s.active, 0, n));
     }
-    if (a.nnz) {
-        std::vector<uint32_t> src(a.nnz);
-        for (uint32_t v = 0; v < a.n[0]; ++v)
-            for (uint64_t e = a.off[0][v]; e < a.off[0][v + 1]; ++e) src[e] = v;
-        CF_HIP_CHECK(ctx, hipMemcpy(f.user_of_edge, src.data(), sizeof(uint32_t) * a.nnz, hipMemcpyHostToDevice));
-    }
+    if (a.nnz) CF_TRY(upload_edge_owners(ctx, f.user_of_edge, a.n[0], a.off[0], a.nnz));
     CF_HIP_CHECK(ctx, hipMemset(f.not_pd, 0, sizeof(unsigned long long)));
     return CF_OK;
-}
-
-template <int DP>
-void launch_update(const IalsLayout& f, int k, int D, const uint32_t rec[4], hipStream_t st) {
-    const IalsSide& s = f.side[k];
-    const AlsLists& L = f.lists[k];
-    const double* Fo = f.side[1 - k].F;
-    const double* Gp = f.Gp[1 - k];
-    if (rec[0])
-        hipLaunchKernelGGL(ials_low_kernel<DP>, dim3((rec[0] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, Fo, Gp, D,
-                           L.low, rec[0], f.not_pd);
-    if (rec[1])
-        hipLaunchKernelGGL((ials_group_kernel<DP, false>), dim3(rec[1]), dim3(kAT), 0, st, s, Fo, Gp, D, L.mid,
-                           (const uint32_t*)nullptr, (double*)nullptr, f.not_pd);
-    if (rec[2]) {
-        hipLaunchKernelGGL((ials_group_kernel<DP, true>), dim3(rec[3]), dim3(kAT), 0, st, s, Fo, Gp, D, L.seg_vertex,
-                           L.seg_index, f.ws, f.not_pd);
-        hipLaunchKernelGGL(ials_finish_kernel<DP>, dim3((rec[2] + kWaves - 1) / kWaves), dim3(kAT), 0, st, s, Gp, D,
-                           L.high, L.high_base, rec[2], f.ws, f.not_pd);
-    }
 }
 
 // The loss of the factors on the device, from G[0] and G[1] as they stand, into *out (device).
@@ -548,7 +433,7 @@ extern "C" int cf_ials_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint
     for (uint32_t h = 0; h < 2 * n_sweeps; ++h) {
         const int k = (int)(h & 1);   // users, then items
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        dispatch_dp(Di, [&](auto dp) { launch_update<decltype(dp)::value>(f, k, Di, rec[k], st); });
+        launch_update(IalsOp{f.side[k], f.Gp[1 - k]}, f.side[1 - k].F, Di, f.lists[k], rec[k], f.ws, f.not_pd, st);
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
         launch_gram(f.side[k].F, a.n[k], Di, f.gpart, f.G[k], f.Gp[k], st);   // for the loss and the next half-sweep
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));

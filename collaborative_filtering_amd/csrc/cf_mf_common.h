@@ -296,6 +296,15 @@ void carve_side(Carver& c, Side& s, uint32_t n, uint64_t nnz) {
     s.active = c.take<uint8_t>(n);
 }
 
+// d_src[e] = the vertex that owns edge e of the CSR `off` (n vertices, nnz > 0 edges).
+inline int upload_edge_owners(cf_ctx* ctx, uint32_t* d_src, uint32_t n, const uint64_t* off, uint64_t nnz) {
+    std::vector<uint32_t> src(nnz);
+    for (uint32_t v = 0; v < n; ++v)
+        for (uint64_t e = off[v]; e < off[v + 1]; ++e) src[e] = v;
+    CF_HIP_CHECK(ctx, hipMemcpy(d_src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+    return CF_OK;
+}
+
 // Uploads that part of a side with n > 0 vertices.  flag = activate, or flag_fill everywhere
 // where activate is NULL.
 template <class Side>
@@ -305,10 +314,7 @@ int upload_side(cf_ctx* ctx, const Side& s, uint64_t nnz, const uint64_t* off, c
     if (nnz) {
         CF_HIP_CHECK(ctx, hipMemcpy((void*)s.nbr, nbr, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemcpy((void*)s.obs, obs, sizeof(float) * nnz, hipMemcpyHostToDevice));
-        std::vector<uint32_t> src(nnz);
-        for (uint32_t v = 0; v < s.n; ++v)
-            for (uint64_t e = off[v]; e < off[v + 1]; ++e) src[e] = v;
-        CF_HIP_CHECK(ctx, hipMemcpy((void*)s.src, src.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+        CF_TRY(upload_edge_owners(ctx, (uint32_t*)s.src, s.n, off, nnz));
     }
     CF_HIP_CHECK(ctx, hipMemcpy(s.nupd, nupd, sizeof(uint32_t) * s.n, hipMemcpyHostToDevice));
     if (activate) CF_HIP_CHECK(ctx, hipMemcpy(s.flag, activate, s.n, hipMemcpyHostToDevice));

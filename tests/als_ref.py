@@ -171,6 +171,7 @@ CASES = {
     "B": (96, 40, 33, False, 0.1, 1e-3, 4, 0),
     "C": (200, 12, 4, True, 0.01, 1e-3, 5, 60),
     "D": (96, 40, 20, "degree", 0.05, 1e-3, None, 0),
+    "E": (96, 40, 13, "degree", 0.05, 1e-3, 6, 0),       # D = 9..16: the kernels' DP = 16 tier
 }
 
 

@@ -118,6 +118,7 @@ CASES = {
     "B": (96, 40, 33, 0, False),     # DP = 64 padding, pref = None
     "B1": (24, 10, 1, 0, False),     # the cut-down graph
     "B8": (24, 10, 8, 0, True),
+    "E": (96, 40, 13, 0, True),      # D = 9..16: the DP = 16 tier, low and mid items
     "H": (2100, 12, 4, 60, True),    # item 0 above the segment length
 }
 

@@ -38,7 +38,7 @@ def case_fit(ctx, name):
     return _FITS[name]
 
 
-@pytest.mark.parametrize("name", ["A", "B", "C", "D"])
+@pytest.mark.parametrize("name", ["A", "B", "C", "D", "E"])
 def test_case_matches_checker(gpu_ctx, name):
     g, U0, V0, *_ = ar.case_inputs(name)
     ref = ar.case_reference(name)
@@ -126,7 +126,8 @@ def test_independent_of_the_active_set(gpu_ctx):
     assert not np.any(part.nupdates_user[~even])
 
 
-def test_segmented_vertex(gpu_ctx):
+@pytest.mark.parametrize("D", [8, 13, 33])   # the high class at DP = 8, 16 and 64
+def test_segmented_vertex(gpu_ctx, D):
     """One item rated by 2 * segment + 37 users: its Gram is summed from three segment partials.
     Every user has this one edge, so after the user half-sweep all user factors are parallel to
     the item's initial factor and the item's Gram has rank one: only the regularisation keeps
@@ -134,7 +135,7 @@ def test_segmented_vertex(gpu_ctx):
     above 1e-3, the conditioning of the four cases the 1e-10 bound was derived on (plain
     lambda = 0.05 would give 3e-6, where rounding alone is worth 1e-9)."""
     seg = _native.load().cf_debug_als_segment()
-    n_users, D = 2 * seg + 37, 8
+    n_users = 2 * seg + 37
     rng = np.random.default_rng(5)
     user = rng.permutation(n_users).astype(np.uint32)
     item = np.zeros(n_users, np.uint32)
