@@ -41,6 +41,9 @@ SIGNATURES = {
     "cf_set_jacobi": (c_int, [c_void_p, c_float, c_int]),
     "cf_set_eigen_refine": (c_int, [c_void_p, c_int, c_float, c_float]),
     "cf_set_eigen_split": (c_int, [c_void_p, c_int]),
+    "cf_set_eigen_lanes": (c_int, [c_void_p, c_int]),
+    "cf_debug_eigen_geometry": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                        POINTER(c_int)]),
     "cf_set_pred_pack": (c_int, [c_void_p, c_int]),
     "cf_debug_split_schedule": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "cf_set_step_masks": (c_int, [c_void_p, c_int]),

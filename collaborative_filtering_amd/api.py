@@ -299,6 +299,11 @@ class Context:
         True the default buckets, or an int 5..12 = the smallest bucket that takes it."""
         self._chk(self.lib.cf_set_eigen_split(self.h, int(enable)), "cf_set_eigen_split")
 
+    def set_eigen_lanes(self, lanes=0):
+        """Lanes per column pair of the full-LDS Jacobi kernel in buckets 1-8 (cf_set_eigen_lanes):
+        0 the per-bucket default, 4 or 8 that count everywhere.  Same output bits either way."""
+        self._chk(self.lib.cf_set_eigen_lanes(self.h, int(lanes)), "cf_set_eigen_lanes")
+
     def set_pred_pack(self, mode=1):
         """Predictor fast path: small per-rating systems two or four to a wave (cf_set_pred_pack):
         1 on (default), 0 one rating per wave.  Same output bits either way."""

@@ -1,7 +1,7 @@
 // cf_eigen.hip -- batched per-user normalized-Laplacian eigendecomposition on gfx950.
 //
 // Replaces compute_eigens() of precompute_local_threads.cpp:100-213 (same math as
-// precompute_local.cpp:165-281).  One workgroup (512 or 1024 threads) owns one user:
+// precompute_local.cpp:165-281).  One workgroup (64 to 1024 threads, EigenGeom) owns one user:
 //
 //   1. gather W_u(i,j) = graph[item_i][item_j] from the HBM-resident dense graph
 //      straight into LDS (k x k fp32, column-major, odd leading dimension);
@@ -15,11 +15,15 @@
 //   4. one-sided (Hestenes) Jacobi sweeps in LDS: each step rotates up to k/2 disjoint
 //      column pairs in a recursive-halving ordering that keeps one column of every pair
 //      in registers for a whole level (see the loop); a pair is owned by 8 lanes
-//      (float2 = ds_read_b64 per row pair, packed v_pk_fma_f32), whose three dot
-//      products are reduced with three DPP steps.  Each step reads and writes the
-//      whole k x k matrix, so the sweep is bound by LDS bandwidth (128 B/clk/CU),
-//      not by VALU issue: 2, 4 and 8 lanes per pair measured 3820, 2828 and 2727
-//      cycles per step (tools/probe_eigen.py, 20k users);
+//      (float2 = ds_read_b64 per row pair, packed v_pk_fma_f32) or, in buckets 5-7, by 4
+//      (ds_read_b128: the rows of two of the 8), whose dot product is reduced with DPP
+//      steps.  A step is the dependent chain of one rotation (read, dot, DPP sum,
+//      sqrt / rcp / rsq, rotate, store) behind a barrier: at equal residency 4 and 8
+//      lanes per pair take the same cycles per step (bucket 8: 2039 against 2036), and
+//      what shortens a bucket is more users per CU.  Blocks are sized to the lane
+//      groups the ordering needs and the 4-lane blocks are half as large again,
+//      so the LDS and not the wave slots sets their residency (geometry
+//      table; tools/probe_eigen_buckets.py);
 //   5. lambda_j = ||b_j|| / ||v_j|| - 1 (||v_j|| tracks the fp32 rotation drift),
 //      rank sort ascending, lim (:184-191), write the k x m row-major block, sigs,
 //      evals and m.
@@ -32,26 +36,42 @@ namespace {
 using namespace cf_eig;
 
 // Bucket geometry: k <= NR = 16 * EMAX rows.  A column is read/written as float2
-// (ds_read_b64 / ds_write_b64): lane l of a pair owns rows 16t + 2l, 16t + 2l + 1.
-// LD == 16 (mod 64) floats: the 4 consecutive columns that the 4 pairs of a
-// half-wave touch in one tournament step start in distinct 16-bank quarters, so the
-// b64 accesses are conflict-free (MI355X_MICROARCH.md, LDS table: b64 bank = (a/4) mod 64).
+// (ds_read_b64 / ds_write_b64): lane l of a pair owns rows 16t + 2l, 16t + 2l + 1; with
+// LANES = 4 as float4, lane l owning rows 16t + 4l .. 16t + 4l + 3.
+// LD == 16 or 48 (mod 64) floats: the 4 consecutive columns that the 4 pairs of a
+// half-wave touch in one tournament step start in distinct 16-bank quarters (0 / 16 / 32 / 48,
+// or 0 / 48 / 32 / 16), so the b64 accesses are conflict-free (MI355X_MICROARCH.md, LDS table:
+// b64 bank = (a/4) mod 64); so are the 16-lane groups of a b128 read (pairs 0, 3, 5, 6 of a
+// quarter-wave) and the 8-lane groups of a b128 store (two adjacent pairs, banks mod 32).
 // NARROW (bucket 12 only): at most NC = 188 columns in LDS, so LD = 208 == 16 (mod 64)
 // fits too.  The full 192-column bucket falls back to LD = NR + 8 == 8 (mod 64), whose
 // b64 column accesses are 2-way bank conflicted; every bucket-12 launch whose largest k
 // is <= 188 (all of BASELINE C2/C4: k is clipped at 180) takes the narrow layout.
-template <int EMAX, bool NARROW = false>
+template <int EMAX, bool NARROW = false, int LANES = kGroup>
 struct EigenGeom {
+    static_assert(LANES == 8 || (LANES == 4 && EMAX <= 8 && !NARROW), "4 lanes per pair: buckets 1-8 only");
     static constexpr int NR = 16 * EMAX;
     static constexpr int NC = NARROW ? 188 : NR;                 // column capacity of B
-    static constexpr int E2 = NR / (2 * kGroup);               // float2 chunks per lane
+    static constexpr int SUB = kGroup / LANES;                 // row sets (lanes of the 8-lane layout) per lane
+    static constexpr int E2 = NR / (2 * kGroup);               // float2 chunks per row set
     static constexpr int LD16 = NR + ((16 - NR) % 64 + 64) % 64;
-    // == 16 mod 64 where it fits in LDS; the full k <= 192 bucket falls back to NR + 8
-    static constexpr int LD = (NC * LD16 + 9 * NR <= 40960 - 4) ? LD16 : NR + 8;
-    static constexpr int NT = (NR > 128) ? 1024 : 512;         // 1 pass per step up to NT/8 pairs
-    // waves per SIMD the sweeps fit in (their register peak): held for the whole kernel, so
-    // the refinement's code cannot push a bucket below it (bucket 5: 6 waves = 3 blocks per CU)
-    static constexpr int WPE = EMAX <= 5 ? 6 : 4;   // 3 or 2 blocks of 512 per CU, or 1 of 1024
+    static constexpr int LD48 = NR + ((48 - NR) % 64 + 64) % 64;
+    // buckets 1-8: the smaller of == 16 and == 48 (mod 64).  Above: == 16 mod 64 where it fits in
+    // LDS; the full k <= 192 bucket falls back to NR + 8
+    static constexpr int LD = EMAX <= 8 ? (LD48 < LD16 ? LD48 : LD16)
+                                        : ((NC * LD16 + 9 * NR <= 40960 - 4) ? LD16 : NR + 8);
+    // lane groups the ordering needs: 2^L * ceil(ceil(n / 2^L) / 2) over the levels L of every
+    // n <= NR (tests/test_eigen_geometry.py walks it): 64 for n <= 128, 32 for n <= 64, 16 below
+    static constexpr int NG = EMAX > 8 ? 128 : EMAX > 4 ? 64 : EMAX > 2 ? 32 : 16;
+    static constexpr int NT = NG * LANES;                      // 1 pass per step; NT >= NR
+    static constexpr int NW = NT / 64;
+    // waves per SIMD the whole kernel is held to (register budget 512 / WPE): the sweeps' own need,
+    // so the refinement's code cannot cost a block per CU.  4 lanes: the budget that lets the LDS
+    // decide the residency (bucket 8: 2 users x 4 waves, 6-7: 3, 5: 5); the 2-wave blocks of buckets
+    // 3-4 are sized for 6 waves per SIMD, so 6 users fit however their waves fall on the SIMDs.
+    static constexpr int WPE = EMAX > 8 ? 4
+                               : LANES == 8 ? (EMAX <= 5 ? 6 : 4)
+                               : (EMAX <= 4 ? 6 : EMAX == 5 ? 5 : EMAX <= 7 ? 3 : 2);
 
     static constexpr size_t bytes() {
         return sizeof(float) * (size_t)NC * LD     // B
@@ -60,18 +80,29 @@ struct EigenGeom {
                + sizeof(int) * NR                  // perm
                + sizeof(int) * 4;                  // flags
     }
+    // users per CU it is sized for: what the LDS holds and the wave slots (evenly placed) carry
+    static constexpr int UPC_LDS = (int)(163840 / bytes());
+    static constexpr int UPC = UPC_LDS < 4 * WPE / NW ? UPC_LDS : 4 * WPE / NW;
 };
+static_assert(EigenGeom<9>::NT == 1024 && EigenGeom<12, true>::NT == 1024 && EigenGeom<8>::NT == 512, "block sizes");
+static_assert(EigenGeom<7, false, 4>::bytes() * 3 <= 163840 && EigenGeom<4, false, 4>::bytes() * 7 <= 163840 &&
+                  EigenGeom<5, false, 4>::bytes() * 5 <= 163840, "users per CU the LDS holds");
 static_assert(EigenGeom<12, true>::LD % 64 == 16, "narrow bucket-12 layout must be conflict-free");
 static_assert(EigenGeom<12, true>::bytes() <= 163840, "narrow bucket-12 layout exceeds 160 KiB LDS");
 
 // RESUME (kUser, buckets >= kSplitEmaxMin): the split-storage kernel (cf_eigen_split.hip) has run
 // stages 1-4 and left B column-major in the user's eigenvector slot, the drifts in evals and the
 // sigs written; this instantiation loads them and runs stages 4b and 5.
-template <int EMAX, bool NARROW = false, bool RESUME = false>
-__global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NARROW>::WPE)) void eigen_kernel(EigenArgs a) {
-    using G = EigenGeom<EMAX, NARROW>;
+// LANES = 4 (buckets 1-8): lane l of a pair owns the rows of the 8-lane layout's lanes 2l and 2l + 1
+// (float2 slots 8e + 2l, 8e + 2l + 1 of a column: one 16-byte access), keeps their partial sums
+// apart (index s below) and adds them in-lane where the 8-lane butterfly has its xor-1 stage, so
+// every reduction keeps its tree and every output its bits.
+template <int EMAX, bool NARROW = false, bool RESUME = false, int LANES = kGroup>
+__global__ __launch_bounds__((EigenGeom<EMAX, NARROW, LANES>::NT), (EigenGeom<EMAX, NARROW, LANES>::WPE)) void eigen_kernel(EigenArgs a) {
+    using G = EigenGeom<EMAX, NARROW, LANES>;
     constexpr int NR = G::NR;
     constexpr int LD = G::LD;
+    constexpr int SUB = G::SUB;
     // element (row i, column j) of B.  (A row swizzle for the LD == 8 (mod 64) bucket,
     // to undo its 2-way bank conflicts, measured 12% slower: the modulo costs more.)
     auto bidx = [](int i, int j) { return j * LD + i; };
@@ -242,8 +273,8 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
     // Group budget: 2^L * ceil(ceil(n / 2^L) / 2) <= NG for every n <= NR (checked
     // offline for every bucket).
     const int n = (k + 1) & ~1;          // columns incl. the padding column k when k is odd
-    const int g = tid / kGroup;
-    const int lig = tid % kGroup;
+    const int g = tid / LANES;
+    const int lig = tid % LANES;
     const float tol = a.tol_scale * sqrtf((float)k) * 2.384185791015625e-07f;  // sqrt(k) * 2^-22
     const float tol2 = tol * tol;
     const bool refine = mode == kUser && a.refine && k > 1;
@@ -258,19 +289,29 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
     // for the fixed columns at every level start, so tracking error stays within a sweep;
     // the eigenvalues (section 5) use fresh fp64 norms.
     float* s_nrm = s_l2d;
-    constexpr int NG = NT / kGroup;
+    // squared norm of the column whose first slot of this lane is bc: one chain per row set
+    auto col_norm2 = [&](const f2* bc) {
+        f2 acc[SUB];
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) acc[s] = f2{0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < E2; ++e) {
+            f2 x[SUB];
+            col_ld<SUB>(bc, e, x);
+#pragma unroll
+            for (int s = 0; s < SUB; ++s) acc[s] = __builtin_elementwise_fma(x[s], x[s], acc[s]);
+        }
+        float part[SUB];
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) part[s] = acc[s].x + acc[s].y;
+        return group_sum<SUB>(part);
+    };
+    constexpr int NG = G::NG;
     int sweep = 0;
     if constexpr (!RESUME) {
     for (; sweep < a.max_sweeps && k > 1; ++sweep) {
         for (int c = g; c < k; c += NG) {
-            const f2* bc = reinterpret_cast<const f2*>(B + c * LD);
-            f2 acc = {0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < E2; ++e) {
-                const f2 x = lds_ld(bc + kGroup * e + lig);
-                acc = __builtin_elementwise_fma(x, x, acc);
-            }
-            const float nc = pair_sum(acc.x + acc.y);
+            const float nc = col_norm2(reinterpret_cast<const f2*>(B + c * LD) + SUB * lig);
             if (lig == 0) s_nrm[c] = nc;
         }
         __syncthreads();
@@ -357,41 +398,57 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
             const int f = (s1 - s0 + 1) >> 1, t = (s1 - s0) - f;
             const int p = s0 + fi;
             const bool fixed = sigma < (1 << L) && fi < f && p < k;
-            auto slot = [&](int, int e) { return kGroup * e + lig; };   // float2 of lane lig, chunk e
-            f2* bp = reinterpret_cast<f2*>(B + (fixed ? p : 0) * LD);
-            f2 xp[E2];
+            // the lane's first float2 of the fixed column; chunk e is kGroup float2 further
+            f2* bp = reinterpret_cast<f2*>(B + (fixed ? p : 0) * LD) + SUB * lig;
+            f2 xp[E2][SUB];
             float devp = 0.0f, al = 0.0f;
             bool pmod = false;
             if (fixed) {
-                f2 al2 = {0.f, 0.f};
+                f2 al2[SUB];
+#pragma unroll
+                for (int s = 0; s < SUB; ++s) al2[s] = f2{0.f, 0.f};
 #pragma unroll
                 for (int e = 0; e < E2; ++e) {
-                    xp[e] = lds_ld(bp + slot(p, e));
-                    al2 = __builtin_elementwise_fma(xp[e], xp[e], al2);
+                    col_ld<SUB>(bp, e, xp[e]);
+#pragma unroll
+                    for (int s = 0; s < SUB; ++s) al2[s] = __builtin_elementwise_fma(xp[e][s], xp[e][s], al2[s]);
                 }
                 devp = s_dev[p];
-                al = pair_sum(al2.x + al2.y);
+                float part[SUB];
+#pragma unroll
+                for (int s = 0; s < SUB; ++s) part[s] = al2[s].x + al2[s].y;
+                al = group_sum<SUB>(part);
             }
             // q = s0 + f + ti walks the traveling half from ti = fi, wrapping at f; a step is
             // live while step < f and the traveling column exists (ti < t, q < k)
             const int tv = fixed ? min(t, k - s0 - f) : 0;
             const int nlive = fixed ? f : 0;
             int ti = fi;
-            f2* bq = reinterpret_cast<f2*>(B + (s0 + f + ti) * LD);
-            f2* const bq0 = reinterpret_cast<f2*>(B + (s0 + f) * LD);
+            f2* bq = reinterpret_cast<f2*>(B + (s0 + f + ti) * LD) + SUB * lig;
+            f2* const bq0 = reinterpret_cast<f2*>(B + (s0 + f) * LD) + SUB * lig;
             for (int step = 0; step < FL; ++step) {
                 const int q = s0 + f + ti;
                 if (step < nlive && ti < tv) {
                     const float dq = s_dev[q];   // issued with the column loads
                     const float be = s_nrm[q];
-                    f2 xq[E2];
-                    f2 ga2[2] = {{0.f, 0.f}, {0.f, 0.f}};   // two chains: half the FMA latency
+                    f2 xq[E2][SUB];
+                    f2 ga2[SUB][2];   // two chains per row set: half the FMA latency
 #pragma unroll
-                    for (int e = 0; e < E2; ++e) xq[e] = lds_ld(bq + slot(q, e));
+                    for (int s = 0; s < SUB; ++s) ga2[s][0] = ga2[s][1] = f2{0.f, 0.f};
 #pragma unroll
-                    for (int e = 0; e < E2; ++e) ga2[e & 1] = __builtin_elementwise_fma(xp[e], xq[e], ga2[e & 1]);
-                    const f2 gs = ga2[0] + ga2[1];
-                    const float ga = pair_sum(gs.x + gs.y);
+                    for (int e = 0; e < E2; ++e) col_ld<SUB>(bq, e, xq[e]);
+#pragma unroll
+                    for (int e = 0; e < E2; ++e)
+#pragma unroll
+                        for (int s = 0; s < SUB; ++s)
+                            ga2[s][e & 1] = __builtin_elementwise_fma(xp[e][s], xq[e][s], ga2[s][e & 1]);
+                    float gpart[SUB];
+#pragma unroll
+                    for (int s = 0; s < SUB; ++s) {
+                        const f2 gs = ga2[s][0] + ga2[s][1];
+                        gpart[s] = gs.x + gs.y;
+                    }
+                    const float ga = group_sum<SUB>(gpart);
                     if (ga * ga > tol2 * (al * be)) {
                         // Hardware rcp/rsq/sqrt: the rotation only has to annihilate ga well
                         // enough; its scale error (c^2 + s^2 != 1) is tracked exactly below.
@@ -406,9 +463,14 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
                         const f2 c2 = {c, c}, s2 = {sn, sn}, ns2 = {-sn, -sn};
 #pragma unroll
                         for (int e = 0; e < E2; ++e) {
-                            const f2 np = __builtin_elementwise_fma(ns2, xq[e], c2 * xp[e]);
-                            lds_st(bq + slot(q, e), __builtin_elementwise_fma(s2, xp[e], c2 * xq[e]));
-                            xp[e] = np;
+                            f2 nq[SUB];
+#pragma unroll
+                            for (int s = 0; s < SUB; ++s) {
+                                const f2 np = __builtin_elementwise_fma(ns2, xq[e][s], c2 * xp[e][s]);
+                                nq[s] = __builtin_elementwise_fma(s2, xp[e][s], c2 * xq[e][s]);
+                                xp[e][s] = np;
+                            }
+                            col_st<SUB>(bq, e, nq);
                         }
                         // c^2 + s^2 = 1 + delta: track each column's accumulated scale so
                         // lambda = ||b_j|| / ||v_j|| - 1 carries no rotation drift.
@@ -444,7 +506,7 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
             }
             if (pmod) {
 #pragma unroll
-                for (int e = 0; e < E2; ++e) lds_st(bp + slot(p, e), xp[e]);
+                for (int e = 0; e < E2; ++e) col_st<SUB>(bp, e, xp[e]);
                 if (lig == 0) {
                     s_dev[p] = devp;
                     s_nrm[p] = al;
@@ -482,97 +544,104 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
     // read B.  (no projector escape at the 1e-2 clustering gap, one sweep fewer.)
     if (refine) {
         for (int c = g; c < k; c += NG) {   // fresh squared norms and mu^2
-            const f2* bc = reinterpret_cast<const f2*>(B + c * LD);
-            f2 acc = {0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < E2; ++e) {
-                const f2 x = lds_ld(bc + kGroup * e + lig);
-                acc = __builtin_elementwise_fma(x, x, acc);
-            }
-            const float nc = pair_sum(acc.x + acc.y);
+            const float nc = col_norm2(reinterpret_cast<const f2*>(B + c * LD) + SUB * lig);
             if (lig == 0) s_mu[c] = nc / (1.0f + s_dev[c]);
         }
         __syncthreads();
         const int nb = (k + 15) >> 4;
         const int m16 = lane & 15, kq = lane >> 4;
-        const int j = wave * 16 + m16;   // this lane's column (wave < nb)
-        const bool jv = wave < nb && j < k;
-        constexpr int HB = (EMAX + 1) / 2;   // row tiles per half
-        f4 kv[EMAX];                         // F(:, j), then -K(:, j): the update's B operands
+        // a block of fewer waves than column tiles (NW < EMAX) gives wave w the tiles w, w + NW:
+        // every tile's MFMA chains and its ksq sum are what its own wave would have run
+        constexpr int TPW = (EMAX + NW - 1) / NW;   // column tiles per wave
+        constexpr int HB = (EMAX + 1) / 2;          // row tiles per half
+        f4 kv[TPW][EMAX];                           // F(:, j), then -K(:, j): the update's B operands
 #pragma unroll
-        for (int I = 0; I < EMAX; ++I) kv[I] = f4{0.f, 0.f, 0.f, 0.f};
-        if (wave < nb) {
-            // F(16 I + 4 kq + r, j) for every row tile I: rows 16 c + 4 kq + {0..3} are the
-            // k-slots of four MFMAs (the same rows on both operands)
-            const f4* pj = reinterpret_cast<const f4*>(B + (jv ? j : 0) * LD + 4 * kq);
-            for (int c = 0; c < nb; ++c) {
-                const f4 y = jv ? pj[4 * c] : f4{0.f, 0.f, 0.f, 0.f};
+        for (int tt = 0; tt < TPW; ++tt) {
+            const int J = wave + tt * NW;     // this wave's column tile
+            const int j = J * 16 + m16;       // this lane's column (J < nb)
+            const bool jv = J < nb && j < k;
 #pragma unroll
-                for (int I0 = 0; I0 < EMAX; I0 += 4) {   // four independent accumulators per group
-                    f4 x[4];
+            for (int I = 0; I < EMAX; ++I) kv[tt][I] = f4{0.f, 0.f, 0.f, 0.f};
+            if (J < nb) {
+                // F(16 I + 4 kq + r, j) for every row tile I: rows 16 c + 4 kq + {0..3} are the
+                // k-slots of four MFMAs (the same rows on both operands)
+                const f4* pj = reinterpret_cast<const f4*>(B + (jv ? j : 0) * LD + 4 * kq);
+                for (int c = 0; c < nb; ++c) {
+                    const f4 y = jv ? pj[4 * c] : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const int ci = (I0 + g4) * 16 + m16;
-                        x[g4] = (I0 + g4 < nb && ci < k) ? reinterpret_cast<const f4*>(B + ci * LD + 4 * kq)[4 * c]
-                                                         : f4{0.f, 0.f, 0.f, 0.f};
+                    for (int I0 = 0; I0 < EMAX; I0 += 4) {   // four independent accumulators per group
+                        f4 x[4];
+#pragma unroll
+                        for (int g4 = 0; g4 < 4; ++g4) {
+                            const int ci = (I0 + g4) * 16 + m16;
+                            x[g4] = (I0 + g4 < nb && ci < k) ? reinterpret_cast<const f4*>(B + ci * LD + 4 * kq)[4 * c]
+                                                             : f4{0.f, 0.f, 0.f, 0.f};
+                        }
+#pragma unroll
+                        for (int t = 0; t < 4; ++t)
+#pragma unroll
+                            for (int g4 = 0; g4 < 4; ++g4)
+                                if (I0 + g4 < EMAX && I0 + g4 < nb)
+                                    kv[tt][I0 + g4] =
+                                        __builtin_amdgcn_mfma_f32_16x16x4f32(x[g4][t], y[t], kv[tt][I0 + g4], 0, 0, 0);
                     }
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4)
-                            if (I0 + g4 < EMAX && I0 + g4 < nb)
-                                kv[I0 + g4] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[g4][t], y[t], kv[I0 + g4], 0, 0, 0);
                 }
+                // K(i, j) = F(i, j) / (mu_i^2 - mu_j^2) for i != j, |mu_i - mu_j| > delta; 0 else
+                const float muj2 = jv ? s_mu[j] : 1.0f;
+                const float muj = sqrtf(muj2);
+                const float dlt = a.refine_delta;
+                float ksq = 0.0f;
+#pragma unroll
+                for (int I = 0; I < EMAX; ++I)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int i = I * 16 + 4 * kq + r;
+                        float kvv = 0.0f;
+                        if (I < nb && jv && i < k && i != j) {
+                            const float mui2 = s_mu[i];
+                            if (fabsf(sqrtf(mui2) - muj) > dlt) kvv = kv[tt][I][r] / (mui2 - muj2);
+                        }
+                        kv[tt][I][r] = -kvv;
+                        ksq = fmaf(kvv, kvv, ksq);
+                    }
+                // sum_i K_ij^2 over the four kq quarters (lanes m16 + 16 q): V's column norm growth
+                ksq += __shfl_xor(ksq, 16);
+                ksq += __shfl_xor(ksq, 32);
+                if (kq == 0 && jv) s_dev[j] += ksq;
             }
-            // K(i, j) = F(i, j) / (mu_i^2 - mu_j^2) for i != j, |mu_i - mu_j| > delta; 0 else
-            const float muj2 = jv ? s_mu[j] : 1.0f;
-            const float muj = sqrtf(muj2);
-            const float dlt = a.refine_delta;
-            float ksq = 0.0f;
-#pragma unroll
-            for (int I = 0; I < EMAX; ++I)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = I * 16 + 4 * kq + r;
-                    float kvv = 0.0f;
-                    if (I < nb && jv && i < k && i != j) {
-                        const float mui2 = s_mu[i];
-                        if (fabsf(sqrtf(mui2) - muj) > dlt) kvv = kv[I][r] / (mui2 - muj2);
-                    }
-                    kv[I][r] = -kvv;
-                    ksq = fmaf(kvv, kvv, ksq);
-                }
-            // sum_i K_ij^2 over the four kq quarters (lanes m16 + 16 q): V's column norm growth
-            ksq += __shfl_xor(ksq, 16);
-            ksq += __shfl_xor(ksq, 32);
-            if (kq == 0 && jv) s_dev[j] += ksq;
         }
         // out(R) = B(R, j) + sum_i B(R, i) (-K(i, j)), A operand B(16 R + m16, 16 I + 4 kq + t),
-        // in two halves of row tiles: a half's rows are stored after every wave has read them
-        // (barrier), and the next half reads only its own rows
+        // in two halves of row tiles: a half's rows are stored after every wave has read them for
+        // all of its column tiles (barrier), and the next half reads only its own rows
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            f4 out[HB];
-            if (wave < nb) {
-                // HB independent accumulator chains: row tile R = h * HB + q
+            f4 out[TPW][HB];
 #pragma unroll
-                for (int q = 0; q < HB; ++q) {
-                    const int R = h * HB + q;
-                    out[q] = (jv && R < nb) ? *reinterpret_cast<const f4*>(B + j * LD + R * 16 + 4 * kq)
-                                            : f4{0.f, 0.f, 0.f, 0.f};
-                }
+            for (int tt = 0; tt < TPW; ++tt) {
+                const int J = wave + tt * NW;
+                const int j = J * 16 + m16;
+                const bool jv = J < nb && j < k;
+                if (J < nb) {
+                    // HB independent accumulator chains: row tile R = h * HB + q
 #pragma unroll
-                for (int I = 0; I < EMAX; ++I) {
-                    if (I < nb) {
+                    for (int q = 0; q < HB; ++q) {
+                        const int R = h * HB + q;
+                        out[tt][q] = (jv && R < nb) ? *reinterpret_cast<const f4*>(B + j * LD + R * 16 + 4 * kq)
+                                                    : f4{0.f, 0.f, 0.f, 0.f};
+                    }
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const int c = I * 16 + 4 * kq + t;
-                            const float* bc = B + c * LD + h * HB * 16 + m16;
+                    for (int I = 0; I < EMAX; ++I) {
+                        if (I < nb) {
 #pragma unroll
-                            for (int q = 0; q < HB; ++q) {
-                                if (h * HB + q < nb) {
-                                    const float av = c < k ? bc[q * 16] : 0.0f;
-                                    out[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, kv[I][t], out[q], 0, 0, 0);
+                            for (int t = 0; t < 4; ++t) {
+                                const int c = I * 16 + 4 * kq + t;
+                                const float* bc = B + c * LD + h * HB * 16 + m16;
+#pragma unroll
+                                for (int q = 0; q < HB; ++q) {
+                                    if (h * HB + q < nb) {
+                                        const float av = c < k ? bc[q * 16] : 0.0f;
+                                        out[tt][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, kv[tt][I][t], out[tt][q], 0, 0, 0);
+                                    }
                                 }
                             }
                         }
@@ -580,11 +649,16 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
                 }
             }
             __syncthreads();   // every wave has read these rows
-            if (jv) {
 #pragma unroll
-                for (int q = 0; q < HB; ++q) {
-                    const int R = h * HB + q;
-                    if (R < nb) *reinterpret_cast<f4*>(B + j * LD + R * 16 + 4 * kq) = out[q];
+            for (int tt = 0; tt < TPW; ++tt) {
+                const int J = wave + tt * NW;
+                const int j = J * 16 + m16;
+                if (J < nb && j < k) {
+#pragma unroll
+                    for (int q = 0; q < HB; ++q) {
+                        const int R = h * HB + q;
+                        if (R < nb) *reinterpret_cast<f4*>(B + j * LD + R * 16 + 4 * kq) = out[tt][q];
+                    }
                 }
             }
         }
@@ -598,21 +672,33 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
     // (local_calc_precomp.cpp:284-304): a fixed convention makes the all-positive
     // lambda = 0 eigenvector of a connected subgraph survive it instead of being dropped
     // from every rating of the user by the luck of the rotation order.
-    // One 8-lane group per column in the sweep's float2 layout (conflict-free, rows past
+    // One lane group per column in the sweep's column layout (conflict-free, rows past
     // nrows are zero), the fp64 partials combined in a fixed butterfly order.
     for (int j = g; j < k; j += NG) {
-        const f2* bc = reinterpret_cast<const f2*>(B + j * LD);
-        double acc = 0.0, sum = 0.0;
+        const f2* bc = reinterpret_cast<const f2*>(B + j * LD) + SUB * lig;
+        double accs[SUB], sums[SUB];
+#pragma unroll
+        for (int s = 0; s < SUB; ++s) accs[s] = sums[s] = 0.0;
 #pragma unroll
         for (int e = 0; e < E2; ++e) {
-            const f2 x = lds_ld(bc + kGroup * e + lig);
-            acc = fma((double)x.x, (double)x.x, acc);
-            acc = fma((double)x.y, (double)x.y, acc);
-            sum += (double)x.x;
-            sum += (double)x.y;
+            f2 x[SUB];
+            col_ld<SUB>(bc, e, x);
+#pragma unroll
+            for (int s = 0; s < SUB; ++s) {
+                accs[s] = fma((double)x[s].x, (double)x[s].x, accs[s]);
+                accs[s] = fma((double)x[s].y, (double)x[s].y, accs[s]);
+                sums[s] += (double)x[s].x;
+                sums[s] += (double)x[s].y;
+            }
+        }
+        // SUB == 2: the butterfly's xor-1 stage is the in-lane add of the two row sets
+        double acc = accs[0], sum = sums[0];
+        if constexpr (SUB == 2) {
+            acc += accs[1];
+            sum += sums[1];
         }
 #pragma unroll
-        for (int o = 1; o < kGroup; o <<= 1) {
+        for (int o = 1; o < LANES; o <<= 1) {
             acc += __shfl_xor(acc, o);
             sum += __shfl_xor(sum, o);
         }
@@ -699,20 +785,52 @@ __global__ __launch_bounds__((EigenGeom<EMAX, NARROW>::NT), (EigenGeom<EMAX, NAR
     }
 }
 
-template <int EMAX, bool NARROW = false, bool RESUME = false>
-int launch_bucket_k(cf_ctx* ctx, const EigenArgs& args, uint32_t count, hipStream_t stream) {
-    using G = EigenGeom<EMAX, NARROW>;
+// Lanes per column pair of the full-LDS kernel, per bucket (index EMAX; 0 unused): the measured
+// best of DESIGN 3.1's geometry table.  Buckets 9-12 have the 8-lane form only.
+constexpr int kDefaultLanes[13] = {0, 8, 8, 8, 8, 4, 4, 4, 8, 8, 8, 8, 8};
+
+// The lane count a setting (0 default, 4, 8) gives bucket emax.
+constexpr int lanes_of(int emax, int setting) {
+    if (emax > 8) return 8;
+    return setting == 0 ? kDefaultLanes[emax] : setting;
+}
+
+int eigen_lanes_setting(cf_ctx* ctx) {
+    if (ctx->eigen_lanes < 0) {   // CF_EIGEN_LANES: 4 or 8 for every bucket 1-8, else the per-bucket default
+        const char* e = getenv("CF_EIGEN_LANES");
+        const int v = e ? atoi(e) : 0;
+        ctx->eigen_lanes = (v == 4 || v == 8) ? v : 0;
+    }
+    return ctx->eigen_lanes;
+}
+
+template <int EMAX, bool NARROW, bool RESUME, int LANES>
+int launch_bucket_kl(cf_ctx* ctx, const EigenArgs& args, uint32_t count, hipStream_t stream) {
+    using G = EigenGeom<EMAX, NARROW, LANES>;
     const size_t lds = G::bytes();
     static_assert(G::bytes() <= 163840, "eigen bucket exceeds 160 KiB LDS");
-    static bool configured = false;
+    static_assert(G::bytes() * G::UPC <= 163840, "intended users per CU exceed the LDS");
+    static_assert(G::NT >= G::NR && G::NT <= 1024, "block size");
+    static bool configured = false;   // one per instantiation, like its kernel's attribute
     if (!configured) {
-        CF_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)eigen_kernel<EMAX, NARROW, RESUME>,
+        CF_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)eigen_kernel<EMAX, NARROW, RESUME, LANES>,
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured = true;
     }
-    hipLaunchKernelGGL((eigen_kernel<EMAX, NARROW, RESUME>), dim3(count), dim3(G::NT), lds, stream, args);
+    hipLaunchKernelGGL((eigen_kernel<EMAX, NARROW, RESUME, LANES>), dim3(count), dim3(G::NT), lds, stream, args);
     CF_HIP_CHECK(ctx, hipGetLastError());
     return CF_OK;
+}
+
+// Buckets 1-8 of the full kernel come in a 4-lane and an 8-lane form (cf_set_eigen_lanes); the
+// RESUME twins and buckets 9-12 keep 8 lanes.
+template <int EMAX, bool NARROW = false, bool RESUME = false>
+int launch_bucket_k(cf_ctx* ctx, const EigenArgs& args, uint32_t count, hipStream_t stream) {
+    if constexpr (EMAX <= 8 && !NARROW && !RESUME) {
+        if (lanes_of(EMAX, eigen_lanes_setting(ctx)) == 4)
+            return launch_bucket_kl<EMAX, NARROW, RESUME, 4>(ctx, args, count, stream);
+    }
+    return launch_bucket_kl<EMAX, NARROW, RESUME, 8>(ctx, args, count, stream);
 }
 
 // kUser launches of buckets >= kSplitEmaxMin go to the split-storage sweeps (two users per CU)
@@ -888,6 +1006,58 @@ int launch_all_buckets(cf_ctx* ctx, const cf_plan* plan, EigenArgs args, hipStre
     return rc;
 }
 }  // namespace
+
+extern "C" int cf_set_eigen_lanes(cf_ctx* ctx, int lanes) {
+    if (!ctx) return CF_EINVAL;
+    if (lanes != 0 && lanes != 4 && lanes != 8) return CF_EINVAL;
+    ctx->eigen_lanes = lanes;
+    return CF_OK;
+}
+
+namespace {
+template <int EMAX, int LANES>
+void geometry_of(int* threads, int* ld, int* lds_bytes, int* users_per_cu) {
+    using G = EigenGeom<EMAX, false, LANES>;
+    *threads = G::NT;
+    *ld = G::LD;
+    *lds_bytes = (int)G::bytes();
+    *users_per_cu = G::UPC;
+}
+template <int EMAX>
+void geometry_of_lanes(int lanes, int* threads, int* ld, int* lds_bytes, int* users_per_cu) {
+    if constexpr (EMAX <= 8) {
+        if (lanes == 4) return geometry_of<EMAX, 4>(threads, ld, lds_bytes, users_per_cu);
+    }
+    geometry_of<EMAX, 8>(threads, ld, lds_bytes, users_per_cu);
+}
+}  // namespace
+
+extern "C" int cf_debug_eigen_geometry(int emax, int lanes_setting, int* lanes, int* threads, int* ld,
+                                       int* lds_bytes, int* users_per_cu) {
+    if (emax < 1 || emax > 12 || (lanes_setting != 0 && lanes_setting != 4 && lanes_setting != 8)) return CF_EINVAL;
+    const int l = lanes_of(emax, lanes_setting);
+    int t = 0, d = 0, b = 0, u = 0;
+    switch (emax) {
+        case 1: geometry_of_lanes<1>(l, &t, &d, &b, &u); break;
+        case 2: geometry_of_lanes<2>(l, &t, &d, &b, &u); break;
+        case 3: geometry_of_lanes<3>(l, &t, &d, &b, &u); break;
+        case 4: geometry_of_lanes<4>(l, &t, &d, &b, &u); break;
+        case 5: geometry_of_lanes<5>(l, &t, &d, &b, &u); break;
+        case 6: geometry_of_lanes<6>(l, &t, &d, &b, &u); break;
+        case 7: geometry_of_lanes<7>(l, &t, &d, &b, &u); break;
+        case 8: geometry_of_lanes<8>(l, &t, &d, &b, &u); break;
+        case 9: geometry_of_lanes<9>(l, &t, &d, &b, &u); break;
+        case 10: geometry_of_lanes<10>(l, &t, &d, &b, &u); break;
+        case 11: geometry_of_lanes<11>(l, &t, &d, &b, &u); break;
+        default: geometry_of_lanes<12>(l, &t, &d, &b, &u); break;
+    }
+    if (lanes) *lanes = l;
+    if (threads) *threads = t;
+    if (ld) *ld = d;
+    if (lds_bytes) *lds_bytes = b;
+    if (users_per_cu) *users_per_cu = u;
+    return CF_OK;
+}
 
 extern "C" int cf_eigen_bucket_timing_split(cf_ctx* ctx, int enable, float* ms13, float* sweeps_ms13) {
     if (!ctx) return CF_EINVAL;

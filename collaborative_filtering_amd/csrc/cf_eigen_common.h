@@ -50,6 +50,52 @@ __device__ __forceinline__ float pair_sum(float x) {
     return x;
 }
 
+// 16-byte column accesses of the 4-lane layout (ds_read_b128 / ds_write_b128), volatile like the
+// 8-byte ones so that none is split or paired
+__device__ __forceinline__ f4 lds_ld4(const f4* p) {
+    return *(const volatile __attribute__((address_space(3))) f4*)(p);
+}
+__device__ __forceinline__ void lds_st4(f4* p, f4 v) {
+    *(volatile __attribute__((address_space(3))) f4*)(p) = v;
+}
+
+// The chunk e of a column for a lane of a LANES-lane pair: x[s] = float2 slot 8e + SUB * lig + s,
+// the rows of lane SUB * lig + s of the 8-lane layout (SUB = 8 / LANES).  col already points at the
+// lane's first slot (column + SUB * lig float2).
+template <int SUB>
+__device__ __forceinline__ void col_ld(const f2* col, int e, f2 (&x)[SUB]) {
+    if constexpr (SUB == 1) {
+        x[0] = lds_ld(col + kGroup * e);
+    } else {
+        const f4 v = lds_ld4(reinterpret_cast<const f4*>(col + kGroup * e));
+        x[0] = f2{v.x, v.y};
+        x[1] = f2{v.z, v.w};
+    }
+}
+template <int SUB>
+__device__ __forceinline__ void col_st(f2* col, int e, const f2 (&x)[SUB]) {
+    if constexpr (SUB == 1) {
+        lds_st(col + kGroup * e, x[0]);
+    } else {
+        lds_st4(reinterpret_cast<f4*>(col + kGroup * e), f4{x[0].x, x[0].y, x[1].x, x[1].y});
+    }
+}
+// All-reduce over a pair's lanes of the per-row-set partials s[]: the tree of pair_sum.  With 4
+// lanes the xor-1 stage of the 8-lane butterfly is the in-lane add of the two row sets; the other
+// two stages run across the quad (after stage 2 lanes {0,1} and {2,3} agree, so l <-> l ^ 2 gives
+// what the half-row mirror gave).
+template <int SUB>
+__device__ __forceinline__ float group_sum(const float (&s)[SUB]) {
+    if constexpr (SUB == 1) {
+        return pair_sum(s[0]);
+    } else {
+        float x = s[0] + s[1];
+        x += dpp_mov<0xB1>(x);   // quad_perm [1,0,3,2]
+        x += dpp_mov<0x4E>(x);   // quad_perm [2,3,0,1]
+        return x;
+    }
+}
+
 // Launch modes (uniform per launch):
 //   kUser  : a2-a4, one user's item subgraph (compute_eigens, precompute_local_threads.cpp)
 //   kLocal : a8, one movie's local graph (local_calc.cpp:268-378): star-shaped W, w > 0.1,

@@ -164,6 +164,7 @@ struct cf_ctx {
     // split-storage Jacobi (cf_eigen_split.hip): per LDS bucket emax, the device copy of the
     // sweep schedule tables of every k the bucket's split kernel takes (built on first use)
     uint32_t* d_split_sched[13] = {};
+    int eigen_lanes = -1;   // -1: not read yet (CF_EIGEN_LANES); 0 per-bucket default, 4 / 8 lanes per pair in buckets 1-8 (cf_set_eigen_lanes)
     int eigen_split = -1;   // -1: not read yet (CF_EIGEN_SPLIT, default on); cf_set_eigen_split
     int pred_pack = -1;     // -1: not read yet (CF_PRED_PACK, default on); cf_set_pred_pack
     int split_finish = -1;  // -1: not read yet (CF_EIGEN_SPLIT_FINISH); 1 / 0 / 2 = refinement + epilogue in the split kernel always / never / buckets <= 8

@@ -99,6 +99,17 @@ int cf_set_eigen_refine(cf_ctx* ctx, int enable, float stop_rel, float delta);
  * CF_EIGEN_SPLIT sets the same.  Same algorithm, same outputs up to the rotation order inside odd
  * segments.  Same call site as cf_eigen_run. */
 int cf_set_eigen_split(cf_ctx* ctx, int enable);
+/* LDS Jacobi, full-LDS kernel, buckets 1-8 (k <= 128; DESIGN 3.1's geometry table): lanes per column
+ * pair.  0 (default) takes the measured best of every bucket, 4 or 8 forces that count in every
+ * bucket 1-8; env CF_EIGEN_LANES sets the same.  The 4-lane form gives a lane the rows of two lanes
+ * of the 8-lane form and keeps every reduction's tree, so the outputs are bit-identical either way.
+ * Buckets 9-12 and the split layout always use 8. */
+int cf_set_eigen_lanes(cf_ctx* ctx, int lanes);
+/* Host only (no device): the geometry a lanes setting (0 | 4 | 8) launches for LDS bucket emax (1-12):
+ * lanes per pair, threads per block, leading dimension of B in floats, LDS bytes per block, and the
+ * users per CU the block and its register budget are sized for.  CF_EINVAL outside those ranges. */
+int cf_debug_eigen_geometry(int emax, int lanes_setting, int* lanes, int* threads, int* ld, int* lds_bytes,
+                            int* users_per_cu);
 /* Predictor fast path, lane packing: mode 1 (default) runs the per-rating systems of
  * n = min(nc, d) <= 14 rows four to a wave and those of 15..30 rows two to a wave; mode 0 gives every
  * rating a wave of its own.  Outputs are bit-identical either way; env CF_PRED_PACK sets the same.
