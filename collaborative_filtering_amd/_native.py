@@ -156,6 +156,11 @@ SIGNATURES = {
     "cf_set_topn_block": (c_int, [c_void_p, c_uint32]),
     "cf_debug_topn_tile_users": (c_int, []),
     "cf_debug_topn_tile_items": (c_int, []),
+    "cf_mf_rank_eval": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+                                c_void_p]),
+    "cf_debug_rank_targets": (c_int, []),
+    "cf_debug_rank_walk": (c_int, []),
     "cf_ials_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 10 + [c_uint32] + [c_void_p] * 4),
     "cf_ials_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 13),
     "cf_mf_gram": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
@@ -229,6 +234,21 @@ class SvdStats(ctypes.Structure):
 class TopnStats(ctypes.Structure):
     """cf_topn_stats (cf_abi.h)."""
     _fields_ = [("blocks", c_uint32), ("n_nan", c_uint64), ("score_ms", c_float), ("select_ms", c_float)]
+
+
+class RankUser(ctypes.Structure):
+    """cf_rank_user (cf_abi.h): 64 bytes; api.RANK_USER_DTYPE is the same layout for numpy."""
+    _fields_ = [("n_cand", c_uint32), ("n_rel", c_uint32), ("hits", c_uint32), ("reserved", c_uint32),
+                ("precision", c_double), ("recall", c_double), ("ndcg", c_double), ("ap", c_double),
+                ("rr", c_double), ("auc", c_double)]
+
+
+class RankSummary(ctypes.Structure):
+    """cf_rank_summary (cf_abi.h)."""
+    _fields_ = [("users_evaluated", c_uint32), ("users_auc", c_uint32), ("edges_counted", c_uint64),
+                ("edges_skipped", c_uint64), ("n_nan_held", c_uint64), ("precision", c_double), ("recall", c_double),
+                ("ndcg", c_double), ("map", c_double), ("mrr", c_double), ("auc", c_double), ("mpr", c_double),
+                ("blocks", c_uint32), ("score_ms", c_float), ("rank_ms", c_float)]
 
 
 EIGEN_SINK =ctypes.CFUNCTYPE(c_int, c_void_p, POINTER(EigenChunk))

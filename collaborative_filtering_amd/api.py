@@ -193,6 +193,28 @@ class TopnResult:
     stats: "_native.TopnStats"
 
 
+# cf_rank_user (cf_abi.h) as a numpy record: the per-user arrays of RankEvalResult are its fields
+RANK_USER_DTYPE = np.dtype([("n_cand", np.uint32), ("n_rel", np.uint32), ("hits", np.uint32), ("reserved", np.uint32),
+                            ("precision", np.float64), ("recall", np.float64), ("ndcg", np.float64),
+                            ("ap", np.float64), ("rr", np.float64), ("auc", np.float64)])
+
+
+@dataclass
+class RankEvalResult:
+    """Outcome of Context.mf_rank_eval.  rank[e] is the 0-based rank of the caller's e-th held-out
+    edge among its user's candidates (UINT32_MAX: the item is excluded or its score is NaN) and
+    n_cand[e] that user's candidate count (0 when none of the user's edges has a rank); users is one
+    RANK_USER_DTYPE record per user (users["ndcg"], ..; all zeros for a user that is not evaluated);
+    summary holds the means over the evaluated users, mpr and the edge counts; stats the
+    cf_rank_summary of the call (blocks, score_ms, rank_ms besides the summary's own fields)."""
+
+    rank: np.ndarray     # uint32[n_edges], the caller's edge order
+    n_cand: np.ndarray   # uint32[n_edges]
+    users: np.ndarray    # RANK_USER_DTYPE[n_users]
+    summary: dict
+    stats: "_native.RankSummary"
+
+
 def _csr(row, col, obs, n_rows):
     """Stable CSR of an edge list by row (edges of one row keep their input order)."""
     perm = np.argsort(row, kind="stable")
@@ -978,6 +1000,64 @@ class Context:
                                       ptr(eoff), ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(items),
                                       ptr(scores), ptr(count), byref(st)), "cf_mf_topn")
         return TopnResult(items, scores, count, st)
+
+    def mf_rank_eval(self, U, V, N, held, *, exclude=None, bias_user=None, bias_item=None,
+                     mean=0.0) -> "RankEvalResult":
+        """cf_mf_rank_eval: the exact rank of every held-out pair among its user's candidates (the
+        scores, exclusions and order of mf_topn) and precision / recall / NDCG / AP / RR / AUC at
+        cutoff N per user with their means and the expected percentile rank (cf_abi.h has the
+        definitions).  held: (user, item[, weight]) arrays of the pairs to find, in any order; a
+        repeated pair raises ValueError.  exclude: (user, item) arrays of the training pairs."""
+        U = np.ascontiguousarray(U, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
+            raise ValueError("U and V must be n_users x D and n_items x D")
+        n_users, n_items, D, N = U.shape[0], V.shape[0], U.shape[1], int(N)
+        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
+        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
+        if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
+            raise ValueError("bias_user / bias_item do not hold one value per user / item")
+        eoff = eitem = None
+        if exclude is not None:
+            eu = np.ascontiguousarray(exclude[0], dtype=np.uint32)
+            ei = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+            if len(eu) != len(ei):
+                raise ValueError("exclude holds different numbers of users and items")
+            if len(eu) and int(eu.max()) >= n_users:
+                raise ValueError("excluded user index out of range")
+            eoff, eitem, _ = _csr(eu, ei, np.zeros(len(eu), np.float32), n_users)
+            if not len(eitem):
+                eitem = np.zeros(1, np.uint32)   # a valid pointer for an empty list
+        hu = np.ascontiguousarray(held[0], dtype=np.uint32)
+        hi = np.ascontiguousarray(held[1], dtype=np.uint32)
+        hw = None if len(held) < 3 or held[2] is None else np.ascontiguousarray(held[2], dtype=np.float64)
+        if len(hu) != len(hi) or (hw is not None and len(hw) != len(hu)):
+            raise ValueError("held holds different numbers of users, items and weights")
+        if len(hu) and int(hu.max()) >= n_users:
+            raise ValueError("held-out user index out of range")
+        perm = np.lexsort((hi, hu))   # by user, then item: the CSR the library wants
+        su, si = hu[perm], hi[perm]
+        if len(su) > 1 and bool(np.any((su[1:] == su[:-1]) & (si[1:] == si[:-1]))):
+            raise ValueError("held holds a pair twice")
+        hoff = np.zeros(n_users + 1, dtype=np.uint64)
+        if n_users:
+            hoff[1:] = np.cumsum(np.bincount(su, minlength=n_users))
+        hitem = np.ascontiguousarray(si) if len(si) else np.zeros(1, np.uint32)
+        hws = None if hw is None else (np.ascontiguousarray(hw[perm]) if len(hw) else np.zeros(1))
+        rank = np.zeros(max(len(su), 1), dtype=np.uint32)
+        users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
+        st = _native.RankSummary()
+        self._chk(self.lib.cf_mf_rank_eval(self.h, n_users, n_items, D, ptr(U), ptr(V), ptr(bu), ptr(bi), float(mean),
+                                           ptr(eoff), ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank),
+                                           ptr(users), byref(st)), "cf_mf_rank_eval")
+        users = users[:n_users]
+        out_rank = np.zeros(len(su), dtype=np.uint32)
+        out_rank[perm] = rank[: len(su)]
+        out_cand = np.zeros(len(su), dtype=np.uint32)
+        out_cand[perm] = users["n_cand"][su]
+        summary = {k: getattr(st, k) for k in ("users_evaluated", "users_auc", "edges_counted", "edges_skipped",
+                                               "n_nan_held", "precision", "recall", "ndcg", "map", "mrr", "auc", "mpr")}
+        return RankEvalResult(out_rank, out_cand, users, summary, st)
 
     # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
     @staticmethod

@@ -1,0 +1,349 @@
+// cf_rank.hip -- ranking evaluation of fitted factors (cf_mf_rank_eval): the exact rank of every
+// held-out edge in its user's full candidate ordering, and precision / recall / NDCG / AP / RR /
+// AUC at a cutoff per user with their means and the expected percentile rank of Hu, Koren and
+// Volinsky.  No program of the reference ranks anything; this closes the pipeline that ials and
+// recommend opened.  DESIGN 3.18.
+//
+// Only the users with a held-out edge are scored: their ascending list goes through the `sel`
+// path of the panel kernels (cf_topn_panel.h), in the user blocks of cf_mf_topn.  On the filled
+// panel:
+//   rank_count_kernel    one workgroup per user row.  The user's held-out items are taken kRankT
+//                        at a time: their keys are fetched from the row (key 0 = excluded, 1 = NaN:
+//                        rank UINT32_MAX), then the row is walked once with kUnroll loads in flight
+//                        per lane while every lane keeps kRankT counters of the keys that come
+//                        before each target (topn_before), then a wave and a block reduction.  The
+//                        first walk also counts the candidates (keys above 1).
+// The device returns integers only and integer sums take any order, so the ranks do not depend on
+// the block size; the metrics are computed on the host from them in fixed orders (rank_metrics).
+// The only atomic is the integer count of NaN held-out items.
+
+#include <algorithm>
+#include <cmath>
+
+#include "cf_topn_panel.h"
+
+namespace {
+
+constexpr int kRankT = 16;               // held-out items counted per walk of a row
+constexpr uint32_t kRankNone = 0xffffffffu;
+
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// Row blockIdx.x of the block is the user b0 + blockIdx.x of the evaluated list; its held-out edges
+// are held_item[held_off[b0 + row] .. held_off[b0 + row + 1]) (held_off: the prefix over the
+// evaluated users, whose edges are the held-out CSR's in the same order).  Every held item is below
+// n_items (checked by the host).
+__global__ __launch_bounds__(kAT) void rank_count_kernel(const uint64_t* __restrict__ panel, uint32_t n_items,
+                                                        const uint64_t* __restrict__ held_off,
+                                                        const uint32_t* __restrict__ held_item, uint32_t b0,
+                                                        uint32_t* __restrict__ out_rank,
+                                                        uint32_t* __restrict__ out_ncand,
+                                                        unsigned long long* __restrict__ n_nan_held) {
+    __shared__ uint64_t s_tkey[kRankT];
+    __shared__ uint32_t s_titem[kRankT];
+    __shared__ uint32_t s_red[kWaves][kRankT + 1];
+    const uint64_t* row = panel + (size_t)blockIdx.x * n_items;
+    const uint64_t e0 = held_off[b0 + blockIdx.x], e1 = held_off[b0 + blockIdx.x + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+
+    for (uint64_t g0 = e0; g0 < e1; g0 += kRankT) {   // the same trips for the whole workgroup
+        if (threadIdx.x < kRankT) {
+            // an empty slot: the largest key at item 0, which nothing comes before
+            uint64_t k = ~0ull;
+            uint32_t it = 0;
+            if (g0 + threadIdx.x < e1) {
+                it = held_item[g0 + threadIdx.x];
+                k = row[it];
+            }
+            s_tkey[threadIdx.x] = k;
+            s_titem[threadIdx.x] = it;
+        }
+        __syncthreads();
+        // the targets are the same in every lane: kept in scalar registers
+        uint32_t tlo[kRankT], thi[kRankT], ti[kRankT];
+#pragma unroll
+        for (int t = 0; t < kRankT; ++t) {
+            const uint64_t k = s_tkey[t];
+            tlo[t] = wave_uniform((uint32_t)k);
+            thi[t] = wave_uniform((uint32_t)(k >> 32));
+            ti[t] = wave_uniform(s_titem[t]);
+        }
+        uint32_t cnt[kRankT], cand = 0;
+#pragma unroll
+        for (int t = 0; t < kRankT; ++t) cnt[t] = 0;
+        uint64_t kv[kUnroll];
+        for (uint64_t i0 = 0; i0 < n_items; i0 += (uint64_t)kAT * kUnroll) {
+            load_keys<kAT>(row, i0 + threadIdx.x, n_items, kv);
+#pragma unroll
+            for (int j = 0; j < kUnroll; ++j) {
+                // past the end of the row: kKeyExcluded, which comes before no candidate
+                const uint32_t i = (uint32_t)(i0 + (uint64_t)j * kAT + threadIdx.x);
+                cand += kv[j] > kKeyNaN;
+#pragma unroll
+                for (int t = 0; t < kRankT; ++t)
+                    cnt[t] += topn_before(kv[j], i, ((uint64_t)thi[t] << 32) | tlo[t], ti[t]);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            cand += __shfl_xor(cand, o);
+#pragma unroll
+            for (int t = 0; t < kRankT; ++t) cnt[t] += __shfl_xor(cnt[t], o);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int t = 0; t < kRankT; ++t) s_red[wave][t] = cnt[t];
+            s_red[wave][kRankT] = cand;
+        }
+        __syncthreads();
+        if (threadIdx.x <= kRankT) {
+            uint32_t sum = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) sum += s_red[w][threadIdx.x];
+            if (threadIdx.x == kRankT) {
+                if (g0 == e0) out_ncand[blockIdx.x] = sum;
+            } else if (g0 + threadIdx.x < e1) {
+                const uint64_t k = s_tkey[threadIdx.x];
+                out_rank[g0 + threadIdx.x] = k > kKeyNaN ? sum : kRankNone;
+                if (k == kKeyNaN) atomicAdd(n_nan_held, 1ull);
+            }
+        }
+        __syncthreads();   // s_tkey and s_red are rewritten by the next group
+    }
+}
+
+struct RankLayout {
+    double* U;
+    double* V;
+    double* bu;
+    double* bi;
+    uint64_t* excl_off;
+    uint32_t* excl_item;
+    uint64_t* sel_off;
+    uint32_t* sel;
+    uint64_t* held_off;
+    uint32_t* held_item;
+    uint64_t* panel;
+    uint32_t* out_rank;
+    uint32_t* out_ncand;
+    unsigned long long* n_nan_held;
+};
+
+// The record of one user from its C candidates and the ranks of its held-out edges (CSR order,
+// kRankNone = skipped), and the user's share of the percentile-rank sums.  `sorted` is scratch.
+// Every sum runs in ascending rank order.
+void rank_metrics(uint32_t C, const uint32_t* rank, const double* w, uint64_t n_edges, uint32_t N,
+                  std::vector<uint32_t>& sorted, cf_rank_user* rec, double* pr_num, double* pr_den) {
+    sorted.clear();
+    for (uint64_t e = 0; e < n_edges; ++e)
+        if (rank[e] != kRankNone) sorted.push_back(rank[e]);
+    *rec = cf_rank_user{};
+    const uint32_t m = (uint32_t)sorted.size();
+    if (m == 0) return;
+    std::sort(sorted.begin(), sorted.end());
+    const uint32_t cut = std::min(m, N);
+    uint32_t hits = 0;
+    double dcg = 0.0, idcg = 0.0, ap = 0.0;
+    uint64_t auc_num = 0;   // sum of C - m - r_j + j: the non-held candidates ranked after r_j
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t r = sorted[j];
+        if (r < N) {
+            ++hits;
+            dcg += 1.0 / std::log2((double)r + 2.0);
+            ap += (double)(j + 1) / ((double)r + 1.0);
+        }
+        auc_num += (uint64_t)C - m - r + j;
+    }
+    for (uint32_t t = 0; t < cut; ++t) idcg += 1.0 / std::log2((double)t + 2.0);
+    rec->n_cand = C;
+    rec->n_rel = m;
+    rec->hits = hits;
+    rec->precision = (double)hits / (double)N;
+    rec->recall = (double)hits / (double)m;
+    rec->ndcg = dcg / idcg;
+    rec->ap = ap / (double)cut;
+    rec->rr = 1.0 / ((double)sorted[0] + 1.0);
+    rec->auc = C > m ? (double)auc_num / ((double)m * (double)(C - m)) : 0.0;
+    for (uint64_t e = 0; e < n_edges; ++e) {   // CSR order
+        if (rank[e] == kRankNone) continue;
+        const double we = w ? w[e] : 1.0;
+        const double pr = C > 1 ? (double)rank[e] / (double)(C - 1) : 0.0;
+        *pr_num += we * pr;
+        *pr_den += we;
+    }
+}
+
+}  // namespace
+
+extern "C" int cf_debug_rank_targets(void) { return kRankT; }
+extern "C" int cf_debug_rank_walk(void) { return kAT * kUnroll; }
+
+extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const double* U,
+                               const double* V, const double* bias_user, const double* bias_item, double mean,
+                               const uint64_t* excl_off, const uint32_t* excl_item, const uint64_t* held_off,
+                               const uint32_t* held_item, const double* held_w, uint32_t N, uint32_t* rank,
+                               cf_rank_user* users, cf_rank_summary* summary) {
+    if (!ctx) return CF_EINVAL;
+    const std::string fn = "cf_mf_rank_eval";
+    if (D == 0) return cf_set_error(ctx, CF_ERANGE, fn + ": D = 0");
+    if (D > CF_ALS_MAX_D) return cf_set_error(ctx, CF_ERANGE, fn + ": D above CF_ALS_MAX_D");
+    if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
+    if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
+    if ((excl_off == nullptr) != (excl_item == nullptr))
+        return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
+    if (!held_off) return cf_set_error(ctx, CF_EINVAL, fn + ": null held-out CSR");
+    if (excl_off && n_users) CF_TRY(check_csr(ctx, "cf_mf_rank_eval", "exclusion", n_users, excl_off, excl_item, n_items));
+    if (held_off[0] != 0) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets do not start at 0");
+    for (uint32_t u = 0; u < n_users; ++u)
+        if (held_off[u + 1] < held_off[u]) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets decrease");
+    const uint64_t n_held = held_off[n_users];
+    if (n_held && !held_item) return cf_set_error(ctx, CF_EINVAL, fn + ": null held-out CSR");
+    for (uint32_t u = 0; u < n_users; ++u)
+        for (uint64_t e = held_off[u]; e < held_off[u + 1]; ++e) {
+            if (held_item[e] >= n_items) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out index out of range");
+            if (e > held_off[u] && held_item[e] <= held_item[e - 1])
+                return cf_set_error(ctx, CF_EINVAL, fn + ": held-out items of a user are not strictly ascending");
+        }
+    if ((n_users && !users) || (n_held && !rank)) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    if (summary) *summary = cf_rank_summary{};
+    for (uint32_t u = 0; u < n_users; ++u) users[u] = cf_rank_user{};
+    if (n_held == 0) return CF_OK;   // no users and no items are among these: an edge needs both
+    if (!U || !V) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    CF_TRY(set_device(ctx));
+
+    // the evaluated users in ascending index: their held-out edges are the CSR's, in its order
+    std::vector<uint32_t> sel;
+    for (uint32_t u = 0; u < n_users; ++u)
+        if (held_off[u + 1] > held_off[u]) sel.push_back(u);
+    const uint32_t n_eval = (uint32_t)sel.size();
+    std::vector<uint64_t> hoff((size_t)n_eval + 1, 0);
+    for (uint32_t j = 0; j < n_eval; ++j) hoff[j + 1] = held_off[sel[j] + 1];
+    const uint64_t nnz = excl_off ? excl_off[n_users] : 0;
+    std::vector<uint64_t> sel_off;   // the evaluated users' own prefix of exclusion counts
+    if (nnz) {
+        sel_off.assign((size_t)n_eval + 1, 0);
+        for (uint32_t j = 0; j < n_eval; ++j) sel_off[j + 1] = sel_off[j] + (excl_off[sel[j] + 1] - excl_off[sel[j]]);
+    }
+    const uint32_t ub = topn_block_users(ctx, n_items, n_eval);
+    const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
+    if ((uint64_t)((ub + kTU - 1) / kTU) * n_it > 0x7fffffffull)
+        return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
+
+    RankLayout L{};
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver c;
+        if (pass) c.base = static_cast<char*>(ctx->d_als);
+        L.U = c.take<double>((size_t)n_users * D);
+        L.V = c.take<double>((size_t)n_items * D);
+        L.bu = bias_user ? c.take<double>(n_users) : nullptr;
+        L.bi = bias_item ? c.take<double>(n_items) : nullptr;
+        L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
+        L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
+        L.sel_off = nnz ? c.take<uint64_t>(sel_off.size()) : nullptr;
+        L.sel = c.take<uint32_t>(n_eval);
+        L.held_off = c.take<uint64_t>(hoff.size());
+        L.held_item = c.take<uint32_t>(n_held);
+        L.panel = c.take<uint64_t>((size_t)ub * n_items);
+        L.out_rank = c.take<uint32_t>(n_held);
+        L.out_ncand = c.take<uint32_t>(ub);
+        L.n_nan_held = c.take<unsigned long long>(1);
+        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
+    }
+    CF_HIP_CHECK(ctx, hipMemcpy(L.U, U, sizeof(double) * (size_t)n_users * D, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(L.V, V, sizeof(double) * (size_t)n_items * D, hipMemcpyHostToDevice));
+    if (bias_user) CF_HIP_CHECK(ctx, hipMemcpy(L.bu, bias_user, sizeof(double) * n_users, hipMemcpyHostToDevice));
+    if (bias_item) CF_HIP_CHECK(ctx, hipMemcpy(L.bi, bias_item, sizeof(double) * n_items, hipMemcpyHostToDevice));
+    if (nnz) {
+        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
+        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+        CF_HIP_CHECK(ctx, hipMemcpy(L.sel_off, sel_off.data(), sizeof(uint64_t) * sel_off.size(), hipMemcpyHostToDevice));
+    }
+    CF_HIP_CHECK(ctx, hipMemcpy(L.sel, sel.data(), sizeof(uint32_t) * n_eval, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(L.held_off, hoff.data(), sizeof(uint64_t) * hoff.size(), hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(L.held_item, held_item, sizeof(uint32_t) * n_held, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemset(L.n_nan_held, 0, sizeof(unsigned long long)));
+
+    MfEvents<3> evs;
+    for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
+    hipStream_t st = nullptr;
+    const double bias_mean = (bias_user || bias_item) ? mean : 0.0;
+    std::vector<uint32_t> n_cand(n_eval);
+    uint32_t blocks = 0;
+    float score_ms = 0.0f, rank_ms = 0.0f;
+    for (uint32_t b0 = 0; b0 < n_eval; b0 += ub) {
+        const uint32_t nb = std::min(ub, n_eval - b0);
+        const uint32_t tiles = ((nb + kTU - 1) / kTU) * n_it;
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
+        hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)L.U, (const double*)L.V,
+                           (int)D, n_items, n_it, (const uint32_t*)L.sel, b0, nb, (const double*)L.bu,
+                           (const double*)L.bi, bias_mean, L.panel);
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
+        const uint64_t edges = nnz ? sel_off[b0 + nb] - sel_off[b0] : 0;
+        if (edges) {
+            if ((edges + kAT - 1) / kAT > 0x7fffffffull)
+                return cf_set_error(ctx, CF_ERANGE, fn + ": exclusions of one user block exceed the launch grid");
+            hipLaunchKernelGGL(topn_exclude_kernel, dim3((unsigned)((edges + kAT - 1) / kAT)), dim3(kAT), 0, st,
+                               (const uint64_t*)L.excl_off, (const uint32_t*)L.excl_item, (const uint64_t*)L.sel_off,
+                               (const uint32_t*)L.sel, b0, nb, n_items, edges, L.panel);
+        }
+        hipLaunchKernelGGL(rank_count_kernel, dim3(nb), dim3(kAT), 0, st, (const uint64_t*)L.panel, n_items,
+                           (const uint64_t*)L.held_off, (const uint32_t*)L.held_item, b0, L.out_rank, L.out_ncand,
+                           L.n_nan_held);
+        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
+        CF_HIP_CHECK(ctx, hipGetLastError());
+        // the copies wait for the stream
+        CF_HIP_CHECK(ctx, hipMemcpy(rank + hoff[b0], L.out_rank + hoff[b0], sizeof(uint32_t) * (hoff[b0 + nb] - hoff[b0]),
+                                    hipMemcpyDeviceToHost));
+        CF_HIP_CHECK(ctx, hipMemcpy(n_cand.data() + b0, L.out_ncand, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+        float a = 0.0f, b = 0.0f;
+        (void)hipEventElapsedTime(&a, evs.e[0], evs.e[1]);
+        (void)hipEventElapsedTime(&b, evs.e[1], evs.e[2]);
+        score_ms += a;
+        rank_ms += b;
+        ++blocks;
+    }
+    unsigned long long n_nan_held = 0;
+    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan_held, L.n_nan_held, sizeof(n_nan_held), hipMemcpyDeviceToHost));
+
+    // the metrics: a few flops per edge, from the integers alone, in ascending user index
+    cf_rank_summary s{};
+    double pr_num = 0.0, pr_den = 0.0;
+    std::vector<uint32_t> sorted;
+    for (uint32_t j = 0; j < n_eval; ++j) {
+        const uint32_t u = sel[j];
+        const uint64_t e0 = held_off[u], ne = held_off[u + 1] - e0;
+        cf_rank_user& rec = users[u];
+        rank_metrics(n_cand[j], rank + e0, held_w ? held_w + e0 : nullptr, ne, N, sorted, &rec, &pr_num, &pr_den);
+        s.edges_counted += rec.n_rel;
+        s.edges_skipped += ne - rec.n_rel;
+        if (rec.n_rel == 0) continue;
+        ++s.users_evaluated;
+        s.precision += rec.precision;
+        s.recall += rec.recall;
+        s.ndcg += rec.ndcg;
+        s.map += rec.ap;
+        s.mrr += rec.rr;
+        if (rec.n_cand > rec.n_rel) {
+            ++s.users_auc;
+            s.auc += rec.auc;
+        }
+    }
+    if (s.users_evaluated) {
+        const double n = (double)s.users_evaluated;
+        s.precision /= n;
+        s.recall /= n;
+        s.ndcg /= n;
+        s.map /= n;
+        s.mrr /= n;
+    }
+    if (s.users_auc) s.auc /= (double)s.users_auc;
+    s.mpr = pr_den != 0.0 ? pr_num / pr_den : 0.0;
+    s.n_nan_held = n_nan_held;
+    s.blocks = blocks;
+    s.score_ms = score_ms;
+    s.rank_ms = rank_ms;
+    if (summary) *summary = s;
+    return CF_OK;
+}

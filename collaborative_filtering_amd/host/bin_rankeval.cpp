@@ -1,0 +1,132 @@
+// rankeval -- how well the factor files of als, ials, sgd, biassgd, svdpp or svd rank held-out
+// edges: the exact rank of every VALIDATE edge among its user's candidate items, and precision,
+// recall, NDCG, MAP, MRR, AUC and the expected percentile rank (Hu, Koren, Volinsky) at a cutoff.
+// No reference counterpart: its programs report RMSE over listed pairs only.
+//   rankeval --factors P --matrix DIR --topn N [--bias] [--mean M] [--weighted] [--output R] [--nshards 4]
+//   P.U_* / P.V_*        factor lines as for recommend (cf_factor_io.hpp); --bias also reads
+//                        P.bias.U_* / P.bias.V_* and adds bias_item + (M + bias_user) to every score
+//   --matrix DIR         the TRAIN edges of DIR are excluded, its VALIDATE edges are held out (their
+//                        value is the edge's weight in mpr under --weighted), its PREDICT edges are
+//                        ignored; a user or item of DIR without a factor line is fatal, and so is a
+//                        VALIDATE pair listed twice
+//   R_<i>_of_<nshards>   "user\titem\trank\tn_cand" per held-out edge, by user then item, sharded by
+//                        user id like the predictions; ranks are 0-based, a skipped edge (excluded, or
+//                        a NaN score) has rank -1
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <tuple>
+
+#include "cf_factor_io.hpp"
+#include "cf_mf_cli.hpp"
+
+int main(int argc, char** argv) {
+    const std::string factors = cfcli::opt(argc, argv, "factors", "");
+    const std::string matrix = cfcli::opt(argc, argv, "matrix", "");
+    const std::string output = cfcli::opt(argc, argv, "output", "");
+    const std::string topn = cfcli::opt(argc, argv, "topn", "");
+    const double mean = std::stod(cfcli::opt(argc, argv, "mean", "0"));
+    const int nshards = std::stoi(cfcli::opt(argc, argv, "nshards", "4"));
+    bool bias = false, weighted = false;
+    for (int i = 1; i < argc; ++i) {
+        bias = bias || std::strcmp(argv[i], "--bias") == 0;
+        weighted = weighted || std::strcmp(argv[i], "--weighted") == 0;
+    }
+    if (factors.empty() || matrix.empty() || topn.empty())
+        cfcli::die("usage: rankeval --factors P --matrix DIR --topn N [--bias] [--mean M] [--weighted] [--output R] [--nshards 4]");
+    const uint32_t N = (uint32_t)std::stoul(topn);
+    if (N == 0 || N > CF_TOPN_MAX_N) cfcli::die("--topn must be between 1 and " + std::to_string(CF_TOPN_MAX_N));
+    if (nshards < 1) cfcli::die("--nshards must be at least 1");
+
+    const cfmf::Factors fu = cfmf::read_factors(factors + ".U");
+    const cfmf::Factors fv = cfmf::read_factors(factors + ".V");
+    if (fu.width != fv.width)
+        cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) + " values per line, " +
+                   factors + ".V " + std::to_string(fv.width));
+    const uint32_t D = fu.width, nu = fu.ids.size(), nm = fv.ids.size();
+    if (D > CF_ALS_MAX_D) cfcli::die("D = " + std::to_string(D) + " is above " + std::to_string(CF_ALS_MAX_D));
+    std::vector<double> bu, bi;
+    if (bias) {
+        bu = cfmf::read_bias(factors + ".bias.U", fu);
+        bi = cfmf::read_bias(factors + ".bias.V", fv);
+    }
+
+    // exclusions: the TRAIN edges as a CSR by user; held out: the VALIDATE edges by user, then item
+    std::vector<uint32_t> eu, em;
+    std::vector<std::tuple<uint32_t, uint32_t, float>> held;
+    for (const cfio::RoleRating& r : cfio::load_movielens_roles(matrix)) {
+        const auto u = fu.ids.at.find(r.user);
+        if (u == fu.ids.at.end())
+            cfcli::die("user " + std::to_string(r.user) + " of " + matrix + " has no line in " + factors + ".U_*");
+        const auto m = fv.ids.at.find(r.item);
+        if (m == fv.ids.at.end())
+            cfcli::die("item " + std::to_string(r.item) + " of " + matrix + " has no line in " + factors + ".V_*");
+        if (r.role == cfio::kTrain) {
+            eu.push_back(u->second);
+            em.push_back(m->second);
+        } else if (r.role == cfio::kValidate) {
+            held.emplace_back(u->second, m->second, r.obs);
+        }
+    }
+    cfmf::Csr excl = cfmf::build_csr(nu, eu, em, std::vector<float>(eu.size(), 0.0f));
+    if (excl.nbr.empty()) excl.nbr.push_back(0);   // a valid pointer for an empty list
+    std::stable_sort(held.begin(), held.end(), [](const auto& a, const auto& b) {
+        return std::get<0>(a) != std::get<0>(b) ? std::get<0>(a) < std::get<0>(b) : std::get<1>(a) < std::get<1>(b);
+    });
+    std::vector<uint64_t> hoff((size_t)nu + 1, 0);
+    std::vector<uint32_t> hitem;
+    std::vector<double> hw;
+    for (size_t e = 0; e < held.size(); ++e) {
+        const uint32_t u = std::get<0>(held[e]), m = std::get<1>(held[e]);
+        if (e && u == std::get<0>(held[e - 1]) && m == std::get<1>(held[e - 1]))
+            cfcli::die("user " + std::to_string(fu.ids.ids[u]) + " item " + std::to_string(fv.ids.ids[m]) + " of " + matrix +
+                       " is a VALIDATE edge twice");
+        hoff[u + 1]++;
+        hitem.push_back(m);
+        hw.push_back((double)std::get<2>(held[e]));
+    }
+    for (uint32_t u = 0; u < nu; ++u) hoff[u + 1] += hoff[u];
+    const uint64_t n_held = hitem.size();
+    if (hitem.empty()) {
+        hitem.push_back(0);
+        hw.push_back(0.0);
+    }
+
+    std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
+    std::vector<uint32_t> rank(hitem.size(), 0);
+    std::vector<cf_rank_user> users((size_t)nu + 1);
+    cf_rank_summary s{};
+    cf_ctx* ctx = cfcli::open_device();
+    cfcli::check(ctx,
+                 cf_mf_rank_eval(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr,
+                                 bias ? bi.data() : nullptr, mean, excl.off.data(), excl.nbr.data(), hoff.data(),
+                                 hitem.data(), weighted ? hw.data() : nullptr, N, rank.data(), users.data(), &s),
+                 "cf_mf_rank_eval");
+    std::printf("Evaluated users: %u held-out edges: %llu skipped: %llu\n", s.users_evaluated,
+                (unsigned long long)n_held, (unsigned long long)s.edges_skipped);
+    std::printf("precision@N %g recall@N %g ndcg@N %g map@N %g mrr %g auc %g mpr %g\n", s.precision, s.recall, s.ndcg,
+                s.map, s.mrr, s.auc, s.mpr);
+    if (s.n_nan_held) std::printf("warning: %llu held-out scores were NaN and have no rank\n", (unsigned long long)s.n_nan_held);
+
+    if (!output.empty()) {
+        cfio::ShardWriter w(".", output, nshards);
+        for (uint32_t u = 0; u < nu; ++u) {
+            const uint32_t uid = fu.ids.ids[u];
+            for (uint64_t e = hoff[u]; e < hoff[u + 1]; ++e) {
+                std::string& out = w.shard(uid);
+                cfio::append_u(out, uid);
+                out += '\t';
+                cfio::append_u(out, fv.ids.ids[hitem[e]]);
+                out += '\t';
+                if (rank[e] == 0xffffffffu) out += "-1";
+                else cfio::append_u(out, rank[e]);
+                out += '\t';
+                cfio::append_u(out, users[u].n_cand);
+                out += '\n';
+            }
+        }
+        w.flush();
+    }
+    cf_destroy(ctx);
+    return 0;
+}

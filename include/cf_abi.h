@@ -39,6 +39,9 @@
  *                                  math.hpp:98-185,805-906
  *   cf_mf_topn                     : none (the reference saves PREDICT edges only, als.cpp:493-510);
  *                                  the N best unrated items per user from the fitted factors
+ *   cf_mf_rank_eval                : none (no program of the reference ranks held-out items); the
+ *                                  rank of every held-out edge and precision / recall / NDCG / MAP /
+ *                                  MRR / AUC / expected percentile rank from the fitted factors
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -794,6 +797,71 @@ int cf_set_topn_block(cf_ctx* ctx, uint32_t users_per_block);
 /* The user and item tile of the scoring kernel (constants of cf_topn.hip; test helpers). */
 int cf_debug_topn_tile_users(void);
 int cf_debug_topn_tile_items(void);
+
+/* ---- ranking evaluation of fitted factors (no reference counterpart: its programs score listed
+ * pairs only, as for cf_mf_topn) ----
+ * For every held-out edge (u, i) its exact rank in u's full candidate ordering, and the ranking
+ * metrics at cutoff N per user with their means.  Scores, candidates and order are those of
+ * cf_mf_topn: score descending, item ascending among equal scores, excluded items and items whose
+ * score is NaN are not candidates.  The item at position p of a user's cf_mf_topn list has rank p.
+ *   excl_off / excl_item : the training edges, a CSR over all n_users as for cf_mf_topn (any order,
+ *       repeats allowed; both NULL = no exclusions)
+ *   held_off / held_item : the edges to find, a CSR over all n_users (u64 offsets, u32 items) whose
+ *       items are STRICTLY ascending within a user, so no edge can be counted twice
+ *   held_w : NULL (all ones) or one weight per held-out edge, used by mpr only
+ * Per user u: C = n_cand, the number of candidates.  The held-out items that are candidates get the
+ * 0-based ranks r_0 < r_1 < .. < r_(m-1), m = n_rel.  A held-out item that is excluded, or whose
+ * score is NaN, gets rank UINT32_MAX; it is not counted in m, it is counted in edges_skipped, and a
+ * NaN one also in n_nan_held.  Ranks are a strict total order by the tie rule: no half credit.
+ * Per user with m >= 1, at cutoff N (1 <= N <= CF_TOPN_MAX_N):
+ *   hits      = #{j : r_j < N}
+ *   precision = hits / N                   recall = hits / m
+ *   ndcg      = (sum_{r_j < N} 1 / log2(r_j + 2)) / (sum_{t < min(m, N)} 1 / log2(t + 2))
+ *   ap        = (1 / min(m, N)) sum_{r_j < N} (j + 1) / (r_j + 1)
+ *   rr        = 1 / (r_0 + 1), with no cutoff
+ *   auc       = sum_j (C - m - r_j + j) / (m (C - m)); defined only if C > m: otherwise the record
+ *               holds 0 and the user is left out of the AUC mean
+ *   percentile rank of edge j = r_j / (C - 1), or 0 when C = 1
+ * A user with m = 0 is not evaluated: its record is all zeros, n_cand included, and it enters no mean.
+ * Summary: the means of precision, recall, ndcg, ap (map), rr (mrr) and auc over the evaluated users,
+ * summed in ascending user index; mpr = sum_e w_e pr_e / sum_e w_e over the counted edges in CSR
+ * order (0 when the weights sum to 0): the expected percentile rank of Hu, Koren and Volinsky as a
+ * fraction in [0, 1], 0 at the top.
+ * Only users with a held-out edge are scored, in the user blocks and key panel of cf_mf_topn (same
+ * cf_set_topn_block, same byte budget).  The device returns integers only (ranks and candidate
+ * counts, integer sums in any order); the metrics are computed on the host from them in the fixed
+ * orders above, so every output is the same bytes across repeats and for every user-block size.
+ * CF_ERANGE: D == 0, D > CF_ALS_MAX_D, N > CF_TOPN_MAX_N.  CF_EINVAL: N == 0, exactly one of
+ * excl_off / excl_item NULL, a NULL held_off (or a NULL held_item with edges), offsets that do not
+ * start at 0 or decrease, an excl_item or held_item >= n_items, held items of a user not strictly
+ * ascending.  A call with no users, no items or no held-out edges succeeds and writes zeros (user
+ * records and summary).  rank: one entry per held-out edge; users: n_users records; summary may be NULL. */
+typedef struct cf_rank_user {
+    uint32_t n_cand;      /* C: candidates of the user (0 when the user is not evaluated) */
+    uint32_t n_rel;       /* m: held-out items that are candidates */
+    uint32_t hits;        /* of them, those ranked below N */
+    uint32_t reserved;    /* 0 */
+    double precision, recall, ndcg, ap, rr, auc;
+} cf_rank_user;
+typedef struct cf_rank_summary {
+    uint32_t users_evaluated;   /* users with m >= 1 */
+    uint32_t users_auc;         /* of them, those with C > m (the AUC mean's count) */
+    uint64_t edges_counted;     /* held-out edges with a rank */
+    uint64_t edges_skipped;     /* held-out edges that are excluded or whose score is NaN */
+    uint64_t n_nan_held;        /* of edges_skipped, the NaN ones (not excluded) */
+    double precision, recall, ndcg, map, mrr, auc, mpr;
+    uint32_t blocks;            /* user blocks processed */
+    float score_ms;             /* device time of the scoring kernels (HIP events) */
+    float rank_ms;              /* device time of exclusion and rank counting */
+} cf_rank_summary;
+int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const double* U, const double* V,
+                    const double* bias_user, const double* bias_item, double mean, const uint64_t* excl_off,
+                    const uint32_t* excl_item, const uint64_t* held_off, const uint32_t* held_item,
+                    const double* held_w, uint32_t N, uint32_t* rank, cf_rank_user* users, cf_rank_summary* summary);
+/* Held-out items counted per walk of a row, and the keys covered by one trip of that walk (threads
+ * x loads in flight per lane): constants of cf_rank.hip; test helpers. */
+int cf_debug_rank_targets(void);
+int cf_debug_rank_walk(void);
 
 /* ---- implicit-feedback ALS (Hu, Koren, Volinsky, ICDM 2008; no reference counterpart: wals.cpp
  * cites the paper and fits observed and sampled edges only) ----
