@@ -16,6 +16,9 @@ HOST_LIB_PATH = os.path.join(_HERE, "libcf_host.so")
 CF_OK = 0
 CF_EINVAL = -1
 CF_ERANGE = -4
+CF_ESTATE = -5
+CF_KNN_SCORE_SUM = 0
+CF_KNN_SCORE_MEAN = 1
 CF_SVD_MAX_NV = 256
 CF_ALS_MAX_D = 64
 CF_TOPN_MAX_N = 1024
@@ -161,6 +164,11 @@ SIGNATURES = {
                                 c_void_p]),
     "cf_debug_rank_targets": (c_int, []),
     "cf_debug_rank_walk": (c_int, []),
+    "cf_knn_topn": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                            c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_knn_rank_eval": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "cf_debug_knn_topn_walk": (c_int, []),
     "cf_ials_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 10 + [c_uint32] + [c_void_p] * 4),
     "cf_ials_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 13),
     "cf_mf_gram": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),

@@ -224,6 +224,57 @@ def _csr(row, col, obs, n_rows):
     return off, np.ascontiguousarray(col[perm]), np.ascontiguousarray(obs[perm])
 
 
+def _exclusion_csr(exclude, n_users):
+    """(excl_off, excl_item) of the (user, item) pairs to leave out, or (None, None)."""
+    if exclude is None:
+        return None, None
+    eu = np.ascontiguousarray(exclude[0], dtype=np.uint32)
+    ei = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+    if len(eu) != len(ei):
+        raise ValueError("exclude holds different numbers of users and items")
+    if len(eu) and int(eu.max()) >= n_users:
+        raise ValueError("excluded user index out of range")
+    eoff, eitem, _ = _csr(eu, ei, np.zeros(len(eu), np.float32), n_users)
+    if not len(eitem):
+        eitem = np.zeros(1, np.uint32)   # a valid pointer for an empty list
+    return eoff, eitem
+
+
+def _held_csr(held, n_users):
+    """The held-out (user, item[, weight]) pairs as the CSR the library wants (by user, then item):
+    (sorted users, the permutation, held_off, held_item, held_w or None)."""
+    hu = np.ascontiguousarray(held[0], dtype=np.uint32)
+    hi = np.ascontiguousarray(held[1], dtype=np.uint32)
+    hw = None if len(held) < 3 or held[2] is None else np.ascontiguousarray(held[2], dtype=np.float64)
+    if len(hu) != len(hi) or (hw is not None and len(hw) != len(hu)):
+        raise ValueError("held holds different numbers of users, items and weights")
+    if len(hu) and int(hu.max()) >= n_users:
+        raise ValueError("held-out user index out of range")
+    perm = np.lexsort((hi, hu))   # by user, then item: the CSR the library wants
+    su, si = hu[perm], hi[perm]
+    if len(su) > 1 and bool(np.any((su[1:] == su[:-1]) & (si[1:] == si[:-1]))):
+        raise ValueError("held holds a pair twice")
+    hoff = np.zeros(n_users + 1, dtype=np.uint64)
+    if n_users:
+        hoff[1:] = np.cumsum(np.bincount(su, minlength=n_users))
+    hitem = np.ascontiguousarray(si) if len(si) else np.zeros(1, np.uint32)
+    hws = None if hw is None else (np.ascontiguousarray(hw[perm]) if len(hw) else np.zeros(1))
+    return su, perm, hoff, hitem, hws
+
+
+def _rank_result(su, perm, rank, users, st):
+    """RankEvalResult from the library's CSR-ordered ranks, back in the caller's edge order."""
+    out_rank = np.zeros(len(su), dtype=np.uint32)
+    out_rank[perm] = rank[: len(su)]
+    out_cand = np.zeros(len(su), dtype=np.uint32)
+    out_cand[perm] = users["n_cand"][su]
+    summary = {k: getattr(st, k) for k in ("users_evaluated", "users_auc", "edges_counted", "edges_skipped",
+                                           "n_nan_held", "precision", "recall", "ndcg", "map", "mrr", "auc", "mpr")}
+    return RankEvalResult(out_rank, out_cand, users, summary, st)
+
+
+_KNN_SCORE_MODES = {"sum": 0, "mean": 1}   # CF_KNN_SCORE_SUM / CF_KNN_SCORE_MEAN
+
 def _mf_factors(mats, ns, names, shapes):
     """The factor matrices of a fit as C-ordered fp64 copies reshaped to (n, D), and D.  D comes
     from whichever side has vertices (an empty side may come as any empty array)."""
@@ -977,17 +1028,7 @@ class Context:
         bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
         if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
             raise ValueError("bias_user / bias_item do not hold one value per user / item")
-        eoff = eitem = None
-        if exclude is not None:
-            eu = np.ascontiguousarray(exclude[0], dtype=np.uint32)
-            ei = np.ascontiguousarray(exclude[1], dtype=np.uint32)
-            if len(eu) != len(ei):
-                raise ValueError("exclude holds different numbers of users and items")
-            if len(eu) and int(eu.max()) >= n_users:
-                raise ValueError("excluded user index out of range")
-            eoff, eitem, _ = _csr(eu, ei, np.zeros(len(eu), np.float32), n_users)
-            if not len(eitem):
-                eitem = np.zeros(1, np.uint32)   # a valid pointer for an empty list
+        eoff, eitem = _exclusion_csr(exclude, n_users)
         sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
         n_out = n_users if sel is None else len(sel)
         if sel is not None and not len(sel):
@@ -1017,47 +1058,73 @@ class Context:
         bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
         if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
             raise ValueError("bias_user / bias_item do not hold one value per user / item")
-        eoff = eitem = None
-        if exclude is not None:
-            eu = np.ascontiguousarray(exclude[0], dtype=np.uint32)
-            ei = np.ascontiguousarray(exclude[1], dtype=np.uint32)
-            if len(eu) != len(ei):
-                raise ValueError("exclude holds different numbers of users and items")
-            if len(eu) and int(eu.max()) >= n_users:
-                raise ValueError("excluded user index out of range")
-            eoff, eitem, _ = _csr(eu, ei, np.zeros(len(eu), np.float32), n_users)
-            if not len(eitem):
-                eitem = np.zeros(1, np.uint32)   # a valid pointer for an empty list
-        hu = np.ascontiguousarray(held[0], dtype=np.uint32)
-        hi = np.ascontiguousarray(held[1], dtype=np.uint32)
-        hw = None if len(held) < 3 or held[2] is None else np.ascontiguousarray(held[2], dtype=np.float64)
-        if len(hu) != len(hi) or (hw is not None and len(hw) != len(hu)):
-            raise ValueError("held holds different numbers of users, items and weights")
-        if len(hu) and int(hu.max()) >= n_users:
-            raise ValueError("held-out user index out of range")
-        perm = np.lexsort((hi, hu))   # by user, then item: the CSR the library wants
-        su, si = hu[perm], hi[perm]
-        if len(su) > 1 and bool(np.any((su[1:] == su[:-1]) & (si[1:] == si[:-1]))):
-            raise ValueError("held holds a pair twice")
-        hoff = np.zeros(n_users + 1, dtype=np.uint64)
-        if n_users:
-            hoff[1:] = np.cumsum(np.bincount(su, minlength=n_users))
-        hitem = np.ascontiguousarray(si) if len(si) else np.zeros(1, np.uint32)
-        hws = None if hw is None else (np.ascontiguousarray(hw[perm]) if len(hw) else np.zeros(1))
+        eoff, eitem = _exclusion_csr(exclude, n_users)
+        su, perm, hoff, hitem, hws = _held_csr(held, n_users)
         rank = np.zeros(max(len(su), 1), dtype=np.uint32)
         users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
         st = _native.RankSummary()
         self._chk(self.lib.cf_mf_rank_eval(self.h, n_users, n_items, D, ptr(U), ptr(V), ptr(bu), ptr(bi), float(mean),
                                            ptr(eoff), ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank),
                                            ptr(users), byref(st)), "cf_mf_rank_eval")
-        users = users[:n_users]
-        out_rank = np.zeros(len(su), dtype=np.uint32)
-        out_rank[perm] = rank[: len(su)]
-        out_cand = np.zeros(len(su), dtype=np.uint32)
-        out_cand[perm] = users["n_cand"][su]
-        summary = {k: getattr(st, k) for k in ("users_evaluated", "users_auc", "edges_counted", "edges_skipped",
-                                               "n_nan_held", "precision", "recall", "ndcg", "map", "mrr", "auc", "mpr")}
-        return RankEvalResult(out_rank, out_cand, users, summary, st)
+        return _rank_result(su, perm, rank, users[:n_users], st)
+
+    # -- top-N and ranking evaluation from the item graph (no reference counterpart) ----
+    def _knn_profile(self, user_off, items, ratings, mode, exclude):
+        """The arguments cf_knn_topn and cf_knn_rank_eval share."""
+        off = np.ascontiguousarray(user_off, dtype=np.uint64)
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        rat = np.ascontiguousarray(ratings, dtype=np.float32)
+        if len(off) < 1 or len(it) != len(rat) or (len(off) and int(off[-1]) != len(it)):
+            raise ValueError("user_off / items / ratings do not describe one profile CSR")
+        if mode not in _KNN_SCORE_MODES:
+            raise ValueError("mode must be 'sum' or 'mean'")
+        n_users = len(off) - 1
+        if isinstance(exclude, str):
+            if exclude != "profile":
+                raise ValueError("exclude must be 'profile', None or (user, item) arrays")
+            eoff, eitem = off, (it if len(it) else np.zeros(1, np.uint32))
+        else:
+            eoff, eitem = _exclusion_csr(exclude, n_users)
+        if not len(it):   # valid pointers for an empty profile
+            it, rat = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        return n_users, off, it, rat, _KNN_SCORE_MODES[mode], eoff, eitem
+
+    def knn_topn(self, user_off, items, ratings, N, *, mode="sum", w_min=0.1, exclude="profile",
+                 users=None) -> "TopnResult":
+        """cf_knn_topn: for every user (or every user of `users`, in its order) the N best items of
+        the uploaded graph by the item-kNN score of the user's profile (user_off / items / ratings,
+        a CSR in the order the sums run): mode "sum" = sum of w(m, i) r over the profile entries with
+        w(m, i) > w_min, "mean" = that over the sum of those w (knn_predict's prediction, 0 without a
+        neighbour).  exclude: "profile" (the user's own items), None, or (user, item) arrays."""
+        n_users, off, it, rat, smode, eoff, eitem = self._knn_profile(user_off, items, ratings, mode, exclude)
+        N = int(N)
+        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
+        n_out = n_users if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.uint32)
+        out_items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
+        count = np.zeros(n_out, dtype=np.uint32)
+        st = _native.TopnStats()
+        self._chk(self.lib.cf_knn_topn(self.h, n_users, ptr(off), ptr(it), ptr(rat), smode, float(w_min), ptr(eoff),
+                                       ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(out_items),
+                                       ptr(scores), ptr(count), byref(st)), "cf_knn_topn")
+        return TopnResult(out_items, scores, count, st)
+
+    def knn_rank_eval(self, user_off, items, ratings, N, held, *, mode="sum", w_min=0.1, exclude="profile",
+                      weights=None) -> "RankEvalResult":
+        """cf_knn_rank_eval: mf_rank_eval with the scores of knn_topn.  held: (user, item) arrays of
+        the pairs to find, in any order; weights: one per held pair (mpr only)."""
+        n_users, off, it, rat, smode, eoff, eitem = self._knn_profile(user_off, items, ratings, mode, exclude)
+        N = int(N)
+        su, perm, hoff, hitem, hws = _held_csr((held[0], held[1], weights), n_users)
+        rank = np.zeros(max(len(su), 1), dtype=np.uint32)
+        users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
+        st = _native.RankSummary()
+        self._chk(self.lib.cf_knn_rank_eval(self.h, n_users, ptr(off), ptr(it), ptr(rat), smode, float(w_min), ptr(eoff),
+                                            ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank), ptr(users),
+                                            byref(st)), "cf_knn_rank_eval")
+        return _rank_result(su, perm, rank, users[:n_users], st)
 
     # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
     @staticmethod

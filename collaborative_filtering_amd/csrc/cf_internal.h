@@ -182,7 +182,44 @@ struct cf_ctx {
     float svdpp_reduce_ms[3] = {0.0f, 0.0f, 0.0f};
     // top-N (cf_topn.hip): users per block forced by cf_set_topn_block (0 = from the byte budget)
     uint32_t topn_block = 0;
+    // item-kNN top-N (cf_knn_topn.hip): the in-lists of the resident graph above knn_in_wmin, a
+    // CSR by column (offsets, scored item m, weight); valid while knn_in_gen == graph_gen, freed by
+    // the next graph upload (cf_knn_in_free)
+    uint64_t* d_knn_in_off = nullptr;
+    uint32_t* d_knn_in_m = nullptr;
+    float* d_knn_in_w = nullptr;
+    uint32_t* d_knn_in_cnt = nullptr;   // per-column counts, then the fill pass's cursors
+    double knn_in_wmin = 0.0;
+    uint64_t knn_in_gen = ~0ull;
+    int knn_topn_wgs = -1;   // -1: not read yet (CF_KNN_TOPN_WGS); workgroups of knn_score_kernel per CU
 };
+
+// Frees the cached in-lists (cf_knn_topn.hip): every graph upload and cf_destroy.
+void cf_knn_in_free(cf_ctx* ctx);
+
+// The score source of the panel drivers (cf_topn_drive, cf_rank_drive): what fills the key panel
+// of a block of users.  The drivers own everything else: the argument checks that do not depend
+// on the source, the user blocks, the exclusions, selection or rank counting, and the copies.
+struct PanelSource {
+    virtual ~PanelSource() = default;
+    virtual bool valid() const = 0;   // false: a null input array (checked after the empty calls return)
+    // bytes the source wants in the ALS workspace beside the driver's own arrays, for blocks of ub users
+    virtual size_t workspace(uint32_t ub) const = 0;
+    // once per call with the workspace reserved: uploads (and whatever is built once per call);
+    // device time that belongs to scoring is added to *score_ms
+    virtual int upload(cf_ctx* ctx, void* ws, uint32_t ub, hipStream_t st, float* score_ms) = 0;
+    // keys of rows [0, nb) of the panel (row stride n_items): the users sel[b0 + r], or b0 + r where sel is null
+    virtual int fill(cf_ctx* ctx, hipStream_t st, const uint32_t* d_sel, uint32_t b0, uint32_t nb, uint64_t* d_panel) = 0;
+};
+// cf_mf_topn / cf_knn_topn after the checks of their own score source (cf_topn.hip), and
+// cf_mf_rank_eval / cf_knn_rank_eval likewise (cf_rank.hip); fn names the caller in messages.
+int cf_topn_drive(cf_ctx* ctx, const char* fn, PanelSource& src, uint32_t n_users, uint32_t n_items,
+                  const uint64_t* excl_off, const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user,
+                  uint32_t N, uint32_t* items, double* scores, uint32_t* count, cf_topn_stats* stats);
+int cf_rank_drive(cf_ctx* ctx, const char* fn, PanelSource& src, uint32_t n_users, uint32_t n_items,
+                  const uint64_t* excl_off, const uint32_t* excl_item, const uint64_t* held_off,
+                  const uint32_t* held_item, const double* held_w, uint32_t N, uint32_t* rank, cf_rank_user* users,
+                  cf_rank_summary* summary);
 
 // One launch of the eigen / predict kernels covers the users of one k-bucket.
 constexpr int kSpillBucket = -1;   // cf_bucket::emax of the k > CF_MAX_K users (the spill paths)

@@ -16,6 +16,7 @@
 // The device returns integers only and integer sums take any order, so the ranks do not depend on
 // the block size; the metrics are computed on the host from them in fixed orders (rank_metrics).
 // The only atomic is the integer count of NaN held-out items.
+// The host driver (cf_rank_drive) takes the panel's filler as a PanelSource, as cf_topn_drive does.
 
 #include <algorithm>
 #include <cmath>
@@ -115,10 +116,7 @@ __global__ __launch_bounds__(kAT) void rank_count_kernel(const uint64_t* __restr
 }
 
 struct RankLayout {
-    double* U;
-    double* V;
-    double* bu;
-    double* bi;
+    void* src;   // the score source's part (PanelSource::workspace)
     uint64_t* excl_off;
     uint32_t* excl_item;
     uint64_t* sel_off;
@@ -189,12 +187,25 @@ extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, 
     const std::string fn = "cf_mf_rank_eval";
     if (D == 0) return cf_set_error(ctx, CF_ERANGE, fn + ": D = 0");
     if (D > CF_ALS_MAX_D) return cf_set_error(ctx, CF_ERANGE, fn + ": D above CF_ALS_MAX_D");
+    MfPanelSource src;
+    src.n_users = n_users, src.n_items = n_items, src.D = D;
+    src.U = U, src.V = V, src.bias_user = bias_user, src.bias_item = bias_item, src.mean = mean;
+    return cf_rank_drive(ctx, "cf_mf_rank_eval", src, n_users, n_items, excl_off, excl_item, held_off, held_item, held_w, N,
+                         rank, users, summary);
+}
+
+// The rank of every held-out edge in the panel that `src` fills, block by block, and the metrics.
+int cf_rank_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_users, uint32_t n_items,
+                  const uint64_t* excl_off, const uint32_t* excl_item, const uint64_t* held_off,
+                  const uint32_t* held_item, const double* held_w, uint32_t N, uint32_t* rank, cf_rank_user* users,
+                  cf_rank_summary* summary) {
+    const std::string fn = name;
     if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
     if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
     if ((excl_off == nullptr) != (excl_item == nullptr))
         return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
     if (!held_off) return cf_set_error(ctx, CF_EINVAL, fn + ": null held-out CSR");
-    if (excl_off && n_users) CF_TRY(check_csr(ctx, "cf_mf_rank_eval", "exclusion", n_users, excl_off, excl_item, n_items));
+    if (excl_off && n_users) CF_TRY(check_csr(ctx, name, "exclusion", n_users, excl_off, excl_item, n_items));
     if (held_off[0] != 0) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets do not start at 0");
     for (uint32_t u = 0; u < n_users; ++u)
         if (held_off[u + 1] < held_off[u]) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets decrease");
@@ -210,7 +221,7 @@ extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, 
     if (summary) *summary = cf_rank_summary{};
     for (uint32_t u = 0; u < n_users; ++u) users[u] = cf_rank_user{};
     if (n_held == 0) return CF_OK;   // no users and no items are among these: an edge needs both
-    if (!U || !V) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    if (!src.valid()) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
     CF_TRY(set_device(ctx));
 
     // the evaluated users in ascending index: their held-out edges are the CSR's, in its order
@@ -232,13 +243,11 @@ extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, 
         return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
 
     RankLayout L{};
+    const size_t src_bytes = src.workspace(ub);
     for (int pass = 0; pass < 2; ++pass) {
         Carver c;
         if (pass) c.base = static_cast<char*>(ctx->d_als);
-        L.U = c.take<double>((size_t)n_users * D);
-        L.V = c.take<double>((size_t)n_items * D);
-        L.bu = bias_user ? c.take<double>(n_users) : nullptr;
-        L.bi = bias_item ? c.take<double>(n_items) : nullptr;
+        L.src = c.take<char>(src_bytes);
         L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
         L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
         L.sel_off = nnz ? c.take<uint64_t>(sel_off.size()) : nullptr;
@@ -251,10 +260,9 @@ extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, 
         L.n_nan_held = c.take<unsigned long long>(1);
         if (!pass) CF_TRY(als_reserve(ctx, c.pos));
     }
-    CF_HIP_CHECK(ctx, hipMemcpy(L.U, U, sizeof(double) * (size_t)n_users * D, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(L.V, V, sizeof(double) * (size_t)n_items * D, hipMemcpyHostToDevice));
-    if (bias_user) CF_HIP_CHECK(ctx, hipMemcpy(L.bu, bias_user, sizeof(double) * n_users, hipMemcpyHostToDevice));
-    if (bias_item) CF_HIP_CHECK(ctx, hipMemcpy(L.bi, bias_item, sizeof(double) * n_items, hipMemcpyHostToDevice));
+    hipStream_t st = nullptr;
+    float score_ms = 0.0f, rank_ms = 0.0f;
+    CF_TRY(src.upload(ctx, L.src, ub, st, &score_ms));
     if (nnz) {
         CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
@@ -267,18 +275,12 @@ extern "C" int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, 
 
     MfEvents<3> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
-    hipStream_t st = nullptr;
-    const double bias_mean = (bias_user || bias_item) ? mean : 0.0;
     std::vector<uint32_t> n_cand(n_eval);
     uint32_t blocks = 0;
-    float score_ms = 0.0f, rank_ms = 0.0f;
     for (uint32_t b0 = 0; b0 < n_eval; b0 += ub) {
         const uint32_t nb = std::min(ub, n_eval - b0);
-        const uint32_t tiles = ((nb + kTU - 1) / kTU) * n_it;
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)L.U, (const double*)L.V,
-                           (int)D, n_items, n_it, (const uint32_t*)L.sel, b0, nb, (const double*)L.bu,
-                           (const double*)L.bi, bias_mean, L.panel);
+        CF_TRY(src.fill(ctx, st, (const uint32_t*)L.sel, b0, nb, L.panel));
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
         const uint64_t edges = nnz ? sel_off[b0 + nb] - sel_off[b0] : 0;
         if (edges) {

@@ -12,6 +12,9 @@
 //                        (key descending, item ascending), and the keys mapped back to doubles
 // A score's bits do not depend on the tile it falls in, the block size or the other users; the
 // only atomics are integer counts (the LDS histogram, the NaN count).
+// The host driver (cf_topn_drive: checks, workspace, user blocks, exclusion, selection, copies) takes
+// the panel's filler as a PanelSource (cf_internal.h): the factors here, the item graph in
+// cf_knn_topn.hip.
 
 #include "cf_topn_panel.h"
 
@@ -210,10 +213,7 @@ __global__ __launch_bounds__(kAT) void topn_select_kernel(const uint64_t* __rest
 }
 
 struct TopnLayout {
-    double* U;
-    double* V;
-    double* bu;
-    double* bi;
+    void* src;   // the score source's part (PanelSource::workspace)
     uint64_t* excl_off;
     uint32_t* excl_item;
     uint64_t* sel_off;
@@ -244,6 +244,18 @@ extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     const std::string fn = "cf_mf_topn";
     if (D == 0) return cf_set_error(ctx, CF_ERANGE, fn + ": D = 0");
     if (D > CF_ALS_MAX_D) return cf_set_error(ctx, CF_ERANGE, fn + ": D above CF_ALS_MAX_D");
+    MfPanelSource src;
+    src.n_users = n_users, src.n_items = n_items, src.D = D;
+    src.U = U, src.V = V, src.bias_user = bias_user, src.bias_item = bias_item, src.mean = mean;
+    return cf_topn_drive(ctx, "cf_mf_topn", src, n_users, n_items, excl_off, excl_item, n_sel, sel_user, N, items, scores,
+                         count, stats);
+}
+
+// The N best candidates of every selected user from the panel that `src` fills, block by block.
+int cf_topn_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_users, uint32_t n_items,
+                  const uint64_t* excl_off, const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user,
+                  uint32_t N, uint32_t* items, double* scores, uint32_t* count, cf_topn_stats* stats) {
+    const std::string fn = name;
     if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
     if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
     if ((excl_off == nullptr) != (excl_item == nullptr))
@@ -253,11 +265,11 @@ extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         for (uint32_t j = 0; j < n_sel; ++j)
             if (sel_user[j] >= n_users) return cf_set_error(ctx, CF_EINVAL, fn + ": selected user out of range");
     if (n_out && !count) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
-    if (excl_off && n_users) CF_TRY(check_csr(ctx, "cf_mf_topn", "exclusion", n_users, excl_off, excl_item, n_items));
+    if (excl_off && n_users) CF_TRY(check_csr(ctx, name, "exclusion", n_users, excl_off, excl_item, n_items));
     if (stats) *stats = cf_topn_stats{};
     for (uint32_t j = 0; j < n_out; ++j) count[j] = 0;
     if (n_out == 0 || n_items == 0) return CF_OK;
-    if (!U || !V || !items || !scores) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
+    if (!src.valid() || !items || !scores) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
     CF_TRY(set_device(ctx));
 
     const uint64_t nnz = excl_off ? excl_off[n_users] : 0;
@@ -274,13 +286,11 @@ extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
 
     TopnLayout L{};
+    const size_t src_bytes = src.workspace(ub);
     for (int pass = 0; pass < 2; ++pass) {
         Carver c;
         if (pass) c.base = static_cast<char*>(ctx->d_als);
-        L.U = c.take<double>((size_t)n_users * D);
-        L.V = c.take<double>((size_t)n_items * D);
-        L.bu = bias_user ? c.take<double>(n_users) : nullptr;
-        L.bi = bias_item ? c.take<double>(n_items) : nullptr;
+        L.src = c.take<char>(src_bytes);
         L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
         L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
         L.sel_off = !sel_off.empty() ? c.take<uint64_t>(sel_off.size()) : nullptr;
@@ -292,10 +302,9 @@ extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         L.n_nan = c.take<unsigned long long>(1);
         if (!pass) CF_TRY(als_reserve(ctx, c.pos));
     }
-    CF_HIP_CHECK(ctx, hipMemcpy(L.U, U, sizeof(double) * (size_t)n_users * D, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(L.V, V, sizeof(double) * (size_t)n_items * D, hipMemcpyHostToDevice));
-    if (bias_user) CF_HIP_CHECK(ctx, hipMemcpy(L.bu, bias_user, sizeof(double) * n_users, hipMemcpyHostToDevice));
-    if (bias_item) CF_HIP_CHECK(ctx, hipMemcpy(L.bi, bias_item, sizeof(double) * n_items, hipMemcpyHostToDevice));
+    hipStream_t st = nullptr;
+    float score_ms = 0.0f, select_ms = 0.0f;
+    CF_TRY(src.upload(ctx, L.src, ub, st, &score_ms));
     if (nnz) {
         CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
         CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
@@ -307,19 +316,13 @@ extern "C" int cf_mf_topn(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
 
     MfEvents<3> evs;
     for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
-    hipStream_t st = nullptr;
     const uint64_t* d_sel_off = L.sel_off ? L.sel_off : L.excl_off;
     const uint64_t* h_sel_off = !sel_off.empty() ? sel_off.data() : excl_off;
-    const double bias_mean = (bias_user || bias_item) ? mean : 0.0;
     uint32_t blocks = 0;
-    float score_ms = 0.0f, select_ms = 0.0f;
     for (uint32_t b0 = 0; b0 < n_out; b0 += ub) {
         const uint32_t nb = std::min(ub, n_out - b0);
-        const uint32_t tiles = ((nb + kTU - 1) / kTU) * n_it;
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)L.U, (const double*)L.V,
-                           (int)D, n_items, n_it, (const uint32_t*)L.sel, b0, nb, (const double*)L.bu,
-                           (const double*)L.bi, bias_mean, L.panel);
+        CF_TRY(src.fill(ctx, st, (const uint32_t*)L.sel, b0, nb, L.panel));
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
         const uint64_t edges = nnz ? h_sel_off[b0 + nb] - h_sel_off[b0] : 0;
         if (edges) {

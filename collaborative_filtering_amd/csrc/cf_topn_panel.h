@@ -1,7 +1,8 @@
 // cf_topn_panel.h -- the score panel that cf_topn.hip (the N best items per user) and cf_rank.hip
 // (the rank of held-out items) share: the order-preserving 64-bit key of a score, the kernel that
 // scores a block of users into a panel of keys, the kernel that marks the excluded pairs in it, the
-// row walk's loads, the order of two (key, item) pairs and the users-per-block rule.
+// row walk's loads, the order of two (key, item) pairs, the users-per-block rule and the factor
+// source of the panel drivers (MfPanelSource; cf_knn_topn.hip has the graph source).
 //
 // The selected users run in blocks of `ub` users whose scores live in a panel of 64-bit keys,
 // key[user in block][item] (row stride n_items, carved from the context's ALS workspace):
@@ -176,5 +177,52 @@ uint32_t topn_block_users(const cf_ctx* ctx, uint32_t n_items, uint32_t n_out) {
     }
     return (uint32_t)std::min<uint64_t>(ub, n_out);
 }
+
+// The factor source of the panel drivers (cf_mf_topn, cf_mf_rank_eval): U, V and the biases in
+// the workspace, topn_score_kernel over the block's tiles.
+struct MfPanelSource final : PanelSource {
+    uint32_t n_users = 0, n_items = 0, D = 0;
+    const double* U = nullptr;
+    const double* V = nullptr;
+    const double* bias_user = nullptr;
+    const double* bias_item = nullptr;
+    double mean = 0.0;
+    double* dU = nullptr;
+    double* dV = nullptr;
+    double* dbu = nullptr;
+    double* dbi = nullptr;
+
+    void carve(Carver& c) {
+        dU = c.take<double>((size_t)n_users * D);
+        dV = c.take<double>((size_t)n_items * D);
+        dbu = bias_user ? c.take<double>(n_users) : nullptr;
+        dbi = bias_item ? c.take<double>(n_items) : nullptr;
+    }
+    bool valid() const override { return U && V; }
+    size_t workspace(uint32_t) const override {
+        MfPanelSource s = *this;
+        Carver c;
+        s.carve(c);
+        return c.pos;
+    }
+    int upload(cf_ctx* ctx, void* ws, uint32_t, hipStream_t, float*) override {
+        Carver c;
+        c.base = static_cast<char*>(ws);
+        carve(c);
+        CF_HIP_CHECK(ctx, hipMemcpy(dU, U, sizeof(double) * (size_t)n_users * D, hipMemcpyHostToDevice));
+        CF_HIP_CHECK(ctx, hipMemcpy(dV, V, sizeof(double) * (size_t)n_items * D, hipMemcpyHostToDevice));
+        if (bias_user) CF_HIP_CHECK(ctx, hipMemcpy(dbu, bias_user, sizeof(double) * n_users, hipMemcpyHostToDevice));
+        if (bias_item) CF_HIP_CHECK(ctx, hipMemcpy(dbi, bias_item, sizeof(double) * n_items, hipMemcpyHostToDevice));
+        return CF_OK;
+    }
+    int fill(cf_ctx*, hipStream_t st, const uint32_t* d_sel, uint32_t b0, uint32_t nb, uint64_t* d_panel) override {
+        const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
+        const uint32_t tiles = ((nb + kTU - 1) / kTU) * n_it;
+        const double bias_mean = (bias_user || bias_item) ? mean : 0.0;
+        hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)dU, (const double*)dV, (int)D,
+                           n_items, n_it, d_sel, b0, nb, (const double*)dbu, (const double*)dbi, bias_mean, d_panel);
+        return CF_OK;
+    }
+};
 
 }  // namespace

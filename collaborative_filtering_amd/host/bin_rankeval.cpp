@@ -3,8 +3,11 @@
 // recall, NDCG, MAP, MRR, AUC and the expected percentile rank (Hu, Koren, Volinsky) at a cutoff.
 // No reference counterpart: its programs report RMSE over listed pairs only.
 //   rankeval --factors P --matrix DIR --topn N [--bias] [--mean M] [--weighted] [--output R] [--nshards 4]
+//   rankeval --graph G --matrix DIR --topn N [--wmin W] [--score sum|mean] [--weighted] [--output R] [--nshards 4]
 //   P.U_* / P.V_*        factor lines as for recommend (cf_factor_io.hpp); --bias also reads
 //                        P.bias.U_* / P.bias.V_* and adds bias_item + (M + bias_user) to every score
+//   --graph G            instead of --factors: the scores of recommend --graph (cf_knn_rank_eval): the
+//                        item graph G* and, as the users' profiles, the TRAIN edges of DIR
 //   --matrix DIR         the TRAIN edges of DIR are excluded, its VALIDATE edges are held out (their
 //                        value is the edge's weight in mpr under --weighted), its PREDICT edges are
 //                        ignored; a user or item of DIR without a factor line is fatal, and so is a
@@ -18,6 +21,7 @@
 #include <tuple>
 
 #include "cf_factor_io.hpp"
+#include "cf_knn_cli.hpp"
 #include "cf_mf_cli.hpp"
 
 int main(int argc, char** argv) {
@@ -32,34 +36,49 @@ int main(int argc, char** argv) {
         bias = bias || std::strcmp(argv[i], "--bias") == 0;
         weighted = weighted || std::strcmp(argv[i], "--weighted") == 0;
     }
-    if (factors.empty() || matrix.empty() || topn.empty())
-        cfcli::die("usage: rankeval --factors P --matrix DIR --topn N [--bias] [--mean M] [--weighted] [--output R] [--nshards 4]");
+    const char* usage =
+        "usage: rankeval --factors P --matrix DIR --topn N [--bias] [--mean M] [--weighted] [--output R] [--nshards 4]\n"
+        "       rankeval --graph G --matrix DIR --topn N [--wmin W] [--score sum|mean] [--weighted] [--output R] [--nshards 4]";
+    if (matrix.empty() || topn.empty()) cfcli::die(usage);
+    const cfknn::Options knn = cfknn::options(argc, argv, factors, matrix, usage);
     const uint32_t N = (uint32_t)std::stoul(topn);
     if (N == 0 || N > CF_TOPN_MAX_N) cfcli::die("--topn must be between 1 and " + std::to_string(CF_TOPN_MAX_N));
     if (nshards < 1) cfcli::die("--nshards must be at least 1");
 
-    const cfmf::Factors fu = cfmf::read_factors(factors + ".U");
-    const cfmf::Factors fv = cfmf::read_factors(factors + ".V");
-    if (fu.width != fv.width)
-        cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) + " values per line, " +
-                   factors + ".V " + std::to_string(fv.width));
-    const uint32_t D = fu.width, nu = fu.ids.size(), nm = fv.ids.size();
-    if (D > CF_ALS_MAX_D) cfcli::die("D = " + std::to_string(D) + " is above " + std::to_string(CF_ALS_MAX_D));
+    const bool from_graph = !knn.graph.empty();
+    cf_ctx* ctx = nullptr;
+    cfmf::Factors fu, fv;
+    cfknn::Source g;
     std::vector<double> bu, bi;
-    if (bias) {
-        bu = cfmf::read_bias(factors + ".bias.U", fu);
-        bi = cfmf::read_bias(factors + ".bias.V", fv);
+    if (from_graph) {
+        ctx = cfcli::open_device();
+        g = cfknn::load(ctx, knn.graph, matrix);
+    } else {
+        fu = cfmf::read_factors(factors + ".U");
+        fv = cfmf::read_factors(factors + ".V");
+        if (fu.width != fv.width)
+            cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) +
+                       " values per line, " + factors + ".V " + std::to_string(fv.width));
+        if (fu.width > CF_ALS_MAX_D)
+            cfcli::die("D = " + std::to_string(fu.width) + " is above " + std::to_string(CF_ALS_MAX_D));
+        if (bias) {
+            bu = cfmf::read_bias(factors + ".bias.U", fu);
+            bi = cfmf::read_bias(factors + ".bias.V", fv);
+        }
     }
+    const cfio::IdMap& uids = from_graph ? g.users : fu.ids;
+    const cfio::IdMap& mids = from_graph ? g.items : fv.ids;
+    const uint32_t D = fu.width, nu = uids.size(), nm = mids.size();
 
     // exclusions: the TRAIN edges as a CSR by user; held out: the VALIDATE edges by user, then item
     std::vector<uint32_t> eu, em;
     std::vector<std::tuple<uint32_t, uint32_t, float>> held;
-    for (const cfio::RoleRating& r : cfio::load_movielens_roles(matrix)) {
-        const auto u = fu.ids.at.find(r.user);
-        if (u == fu.ids.at.end())
+    for (const cfio::RoleRating& r : from_graph ? g.roles : cfio::load_movielens_roles(matrix)) {
+        const auto u = uids.at.find(r.user);
+        if (u == uids.at.end())
             cfcli::die("user " + std::to_string(r.user) + " of " + matrix + " has no line in " + factors + ".U_*");
-        const auto m = fv.ids.at.find(r.item);
-        if (m == fv.ids.at.end())
+        const auto m = mids.at.find(r.item);
+        if (m == mids.at.end())
             cfcli::die("item " + std::to_string(r.item) + " of " + matrix + " has no line in " + factors + ".V_*");
         if (r.role == cfio::kTrain) {
             eu.push_back(u->second);
@@ -79,7 +98,7 @@ int main(int argc, char** argv) {
     for (size_t e = 0; e < held.size(); ++e) {
         const uint32_t u = std::get<0>(held[e]), m = std::get<1>(held[e]);
         if (e && u == std::get<0>(held[e - 1]) && m == std::get<1>(held[e - 1]))
-            cfcli::die("user " + std::to_string(fu.ids.ids[u]) + " item " + std::to_string(fv.ids.ids[m]) + " of " + matrix +
+            cfcli::die("user " + std::to_string(uids.ids[u]) + " item " + std::to_string(mids.ids[m]) + " of " + matrix +
                        " is a VALIDATE edge twice");
         hoff[u + 1]++;
         hitem.push_back(m);
@@ -92,16 +111,25 @@ int main(int argc, char** argv) {
         hw.push_back(0.0);
     }
 
-    std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
+    if (from_graph) std::printf("Users: %u items: %u\n", nu, nm);
+    else std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
     std::vector<uint32_t> rank(hitem.size(), 0);
     std::vector<cf_rank_user> users((size_t)nu + 1);
     cf_rank_summary s{};
-    cf_ctx* ctx = cfcli::open_device();
-    cfcli::check(ctx,
-                 cf_mf_rank_eval(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr,
-                                 bias ? bi.data() : nullptr, mean, excl.off.data(), excl.nbr.data(), hoff.data(),
-                                 hitem.data(), weighted ? hw.data() : nullptr, N, rank.data(), users.data(), &s),
-                 "cf_mf_rank_eval");
+    if (from_graph) {
+        cfcli::check(ctx,
+                     cf_knn_rank_eval(ctx, nu, g.profile.off.data(), g.profile.nbr.data(), g.profile.obs.data(),
+                                      knn.score_mode, knn.w_min, excl.off.data(), excl.nbr.data(), hoff.data(), hitem.data(),
+                                      weighted ? hw.data() : nullptr, N, rank.data(), users.data(), &s),
+                     "cf_knn_rank_eval");
+    } else {
+        ctx = cfcli::open_device();
+        cfcli::check(ctx,
+                     cf_mf_rank_eval(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr,
+                                     bias ? bi.data() : nullptr, mean, excl.off.data(), excl.nbr.data(), hoff.data(),
+                                     hitem.data(), weighted ? hw.data() : nullptr, N, rank.data(), users.data(), &s),
+                     "cf_mf_rank_eval");
+    }
     std::printf("Evaluated users: %u held-out edges: %llu skipped: %llu\n", s.users_evaluated,
                 (unsigned long long)n_held, (unsigned long long)s.edges_skipped);
     std::printf("precision@N %g recall@N %g ndcg@N %g map@N %g mrr %g auc %g mpr %g\n", s.precision, s.recall, s.ndcg,
@@ -111,12 +139,12 @@ int main(int argc, char** argv) {
     if (!output.empty()) {
         cfio::ShardWriter w(".", output, nshards);
         for (uint32_t u = 0; u < nu; ++u) {
-            const uint32_t uid = fu.ids.ids[u];
+            const uint32_t uid = uids.ids[u];
             for (uint64_t e = hoff[u]; e < hoff[u + 1]; ++e) {
                 std::string& out = w.shard(uid);
                 cfio::append_u(out, uid);
                 out += '\t';
-                cfio::append_u(out, fv.ids.ids[hitem[e]]);
+                cfio::append_u(out, mids.ids[hitem[e]]);
                 out += '\t';
                 if (rank[e] == 0xffffffffu) out += "-1";
                 else cfio::append_u(out, rank[e]);

@@ -2,11 +2,17 @@
 // svdpp or svd (--predictions P there).  No reference counterpart: its programs save the PREDICT
 // edges only (als.cpp:493-510), so scoring every item of every user meant listing every pair.
 //   recommend --factors P [--matrix DIR] --topn N [--bias] [--mean M] --output R [--nshards 4] [--users FILE]
+//   recommend --graph G --matrix DIR --topn N [--wmin W] [--score sum|mean] --output R [--nshards 4] [--users FILE]
 //   P.U_* / P.V_*        factor lines "id f0 f1 .. " or "id) f0 f1 .. " (cf_factor_io.hpp); D is the
 //                        first line's width; --bias also reads P.bias.U_* / P.bias.V_* and adds
 //                        bias_item + (M + bias_user) to every score (biassgd.cpp:400-403)
 //   --matrix DIR         every TRAIN and VALIDATE edge of DIR is excluded (.predict pairs stay
 //                        candidates); a user or item of DIR without a factor line is fatal
+//   --graph G            instead of --factors: the item graph G* (the out_fin_ shards of knn2) scores
+//                        every item for a user from the user's TRAIN edges of DIR, by cf_knn_topn
+//                        (cf_knn_cli.hpp): --score sum = sum of w r over the rated items with w > W
+//                        (default 0.1), mean = that over the sum of those w (knn3's prediction);
+//                        users are those of DIR, items those of G* and DIR together
 //   --users FILE         one user id per line: only their lists, in that order (default: every
 //                        user of P.U_*, ascending id)
 //   R_<i>_of_<nshards>   "user\titem\tscore" per listed item in rank order per user, score as %g,
@@ -15,6 +21,7 @@
 #include <cstring>
 
 #include "cf_factor_io.hpp"
+#include "cf_knn_cli.hpp"
 #include "cf_mf_cli.hpp"
 
 int main(int argc, char** argv) {
@@ -27,35 +34,51 @@ int main(int argc, char** argv) {
     const int nshards = std::stoi(cfcli::opt(argc, argv, "nshards", "4"));
     bool bias = false;
     for (int i = 1; i < argc; ++i) bias = bias || std::strcmp(argv[i], "--bias") == 0;
-    if (factors.empty() || output.empty() || topn.empty())
-        cfcli::die("usage: recommend --factors P [--matrix DIR] --topn N [--bias] [--mean M] --output R [--nshards 4] [--users FILE]");
+    const char* usage =
+        "usage: recommend --factors P [--matrix DIR] --topn N [--bias] [--mean M] --output R [--nshards 4] [--users FILE]\n"
+        "       recommend --graph G --matrix DIR --topn N [--wmin W] [--score sum|mean] --output R [--nshards 4] [--users FILE]";
+    if (output.empty() || topn.empty()) cfcli::die(usage);
+    const cfknn::Options knn = cfknn::options(argc, argv, factors, matrix, usage);
     const uint32_t N = (uint32_t)std::stoul(topn);
     if (N == 0 || N > CF_TOPN_MAX_N) cfcli::die("--topn must be between 1 and " + std::to_string(CF_TOPN_MAX_N));
     if (nshards < 1) cfcli::die("--nshards must be at least 1");
 
-    const cfmf::Factors fu = cfmf::read_factors(factors + ".U");
-    const cfmf::Factors fv = cfmf::read_factors(factors + ".V");
-    if (fu.width != fv.width)
-        cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) + " values per line, " +
-                   factors + ".V " + std::to_string(fv.width));
-    const uint32_t D = fu.width, nu = fu.ids.size(), nm = fv.ids.size();
-    if (D > CF_ALS_MAX_D) cfcli::die("D = " + std::to_string(D) + " is above " + std::to_string(CF_ALS_MAX_D));
+    const bool from_graph = !knn.graph.empty();
+    cf_ctx* ctx = nullptr;
+    cfmf::Factors fu, fv;
+    cfknn::Source g;
     std::vector<double> bu, bi;
-    if (bias) {
-        bu = cfmf::read_bias(factors + ".bias.U", fu);
-        bi = cfmf::read_bias(factors + ".bias.V", fv);
+    if (from_graph) {
+        ctx = cfcli::open_device();
+        g = cfknn::load(ctx, knn.graph, matrix);
+    } else {
+        fu = cfmf::read_factors(factors + ".U");
+        fv = cfmf::read_factors(factors + ".V");
+        if (fu.width != fv.width)
+            cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) +
+                       " values per line, " + factors + ".V " + std::to_string(fv.width));
+        if (fu.width > CF_ALS_MAX_D)
+            cfcli::die("D = " + std::to_string(fu.width) + " is above " + std::to_string(CF_ALS_MAX_D));
+        if (bias) {
+            bu = cfmf::read_bias(factors + ".bias.U", fu);
+            bi = cfmf::read_bias(factors + ".bias.V", fv);
+        }
     }
+    const cfio::IdMap& uids = from_graph ? g.users : fu.ids;
+    const cfio::IdMap& mids = from_graph ? g.items : fv.ids;
+    const std::string ufile = from_graph ? matrix : factors + ".U_*";   // where a user id comes from
+    const uint32_t D = fu.width, nu = uids.size(), nm = mids.size();
 
     // exclusions: the TRAIN and VALIDATE edges, as a CSR by user
     cfmf::Csr excl;
     if (!matrix.empty()) {
         std::vector<uint32_t> eu, em;
-        for (const cfio::RoleRating& r : cfio::load_movielens_roles(matrix)) {
-            const auto u = fu.ids.at.find(r.user);
-            if (u == fu.ids.at.end())
+        for (const cfio::RoleRating& r : from_graph ? g.roles : cfio::load_movielens_roles(matrix)) {
+            const auto u = uids.at.find(r.user);
+            if (u == uids.at.end())
                 cfcli::die("user " + std::to_string(r.user) + " of " + matrix + " has no line in " + factors + ".U_*");
-            const auto m = fv.ids.at.find(r.item);
-            if (m == fv.ids.at.end())
+            const auto m = mids.at.find(r.item);
+            if (m == mids.at.end())
                 cfcli::die("item " + std::to_string(r.item) + " of " + matrix + " has no line in " + factors + ".V_*");
             if (r.role == cfio::kPredict) continue;
             eu.push_back(u->second);
@@ -79,8 +102,8 @@ int main(int argc, char** argv) {
             const auto r = std::from_chars(p, e, id);
             if (r.ec != std::errc()) cfcli::die("--users: " + users_file + " holds something that is not a user id");
             p = r.ptr;
-            const auto u = fu.ids.at.find(id);
-            if (u == fu.ids.at.end()) cfcli::die("user " + std::to_string(id) + " of " + users_file + " has no line in " + factors + ".U_*");
+            const auto u = uids.at.find(id);
+            if (u == uids.at.end()) cfcli::die("user " + std::to_string(id) + " of " + users_file + " has no line in " + ufile);
             sel.push_back(u->second);
         }
     }
@@ -88,29 +111,38 @@ int main(int argc, char** argv) {
     const uint32_t n_out = selected ? (uint32_t)sel.size() : nu;
     if (selected && sel.empty()) sel.push_back(0);
 
-    std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
+    if (from_graph) std::printf("Users: %u items: %u\n", nu, nm);
+    else std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
     std::vector<uint32_t> items((size_t)n_out * N), count(n_out);
     std::vector<double> scores((size_t)n_out * N);
-    cf_ctx* ctx = cfcli::open_device();
     cf_topn_stats st{};
-    cfcli::check(ctx,
-                 cf_mf_topn(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr, bias ? bi.data() : nullptr,
-                            mean, matrix.empty() ? nullptr : excl.off.data(), matrix.empty() ? nullptr : excl.nbr.data(),
-                            selected ? n_out : 0, selected ? sel.data() : nullptr, N, items.data(), scores.data(),
-                            count.data(), &st),
-                 "cf_mf_topn");
+    if (from_graph) {
+        cfcli::check(ctx,
+                     cf_knn_topn(ctx, nu, g.profile.off.data(), g.profile.nbr.data(), g.profile.obs.data(), knn.score_mode,
+                                 knn.w_min, excl.off.data(), excl.nbr.data(), selected ? n_out : 0,
+                                 selected ? sel.data() : nullptr, N, items.data(), scores.data(), count.data(), &st),
+                     "cf_knn_topn");
+    } else {
+        ctx = cfcli::open_device();
+        cfcli::check(ctx,
+                     cf_mf_topn(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr,
+                                bias ? bi.data() : nullptr, mean, matrix.empty() ? nullptr : excl.off.data(),
+                                matrix.empty() ? nullptr : excl.nbr.data(), selected ? n_out : 0,
+                                selected ? sel.data() : nullptr, N, items.data(), scores.data(), count.data(), &st),
+                     "cf_mf_topn");
+    }
     std::printf("User blocks: %u  scoring kernels: %.3f ms  exclusion and selection kernels: %.3f ms\n", st.blocks,
                 st.score_ms, st.select_ms);
     if (st.n_nan) std::printf("warning: %llu scores were NaN and are not listed\n", (unsigned long long)st.n_nan);
 
     cfio::ShardWriter w(".", output, nshards);
     for (uint32_t j = 0; j < n_out; ++j) {
-        const uint32_t uid = fu.ids.ids[selected ? sel[j] : j];
+        const uint32_t uid = uids.ids[selected ? sel[j] : j];
         std::string& out = w.shard(uid);
         for (uint32_t r = 0; r < count[j]; ++r) {
             cfio::append_u(out, uid);
             out += '\t';
-            cfio::append_u(out, fv.ids.ids[items[(size_t)j * N + r]]);
+            cfio::append_u(out, mids.ids[items[(size_t)j * N + r]]);
             out += '\t';
             cfio::append_g(out, scores[(size_t)j * N + r]);
             out += '\n';

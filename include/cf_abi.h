@@ -42,6 +42,8 @@
  *   cf_mf_rank_eval                : none (no program of the reference ranks held-out items); the
  *                                  rank of every held-out edge and precision / recall / NDCG / MAP /
  *                                  MRR / AUC / expected percentile rank from the fitted factors
+ *   cf_knn_topn                    : none: knn3 scores listed pairs only
+ *   cf_knn_rank_eval               : none: knn3 scores listed pairs only
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -862,6 +864,48 @@ int cf_mf_rank_eval(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D,
  * x loads in flight per lane): constants of cf_rank.hip; test helpers. */
 int cf_debug_rank_targets(void);
 int cf_debug_rank_walk(void);
+
+/* ---- top-N recommendation and ranking evaluation from the item graph (no reference counterpart:
+ * knn3 scores listed pairs only, knn3.cpp:185-227) ----
+ * The neighbourhood model as a score source of cf_mf_topn and cf_mf_rank_eval.  n_items is the
+ * resident graph's item count.  User u's profile is prof_item / prof_rating[prof_off[u] ..
+ * prof_off[u+1]) = (i_0, r_0), (i_1, r_1), .., in the order given; for every item m of the graph
+ *   sw(u, m)  = sum_t [(double) w(m, i_t) > w_min] (double) w(m, i_t)
+ *   swr(u, m) = sum_t [(double) w(m, i_t) > w_min] (double) w(m, i_t) * (double) r_t
+ * both over t ascending from a zero accumulator in fp64; w(m, i) is row m, column i of the uploaded
+ * graph as parsed (fp32): the out-edge of the scored item, the direction of cf_knn_predict.  The
+ * graph is not symmetrized, i_t == m is no special case (its weight is what the graph holds), and a
+ * profile item listed twice counts twice.
+ *   CF_KNN_SCORE_SUM  : score = swr
+ *   CF_KNN_SCORE_MEAN : score = sw > 0 ? swr / sw : 0, the prediction of cf_knn_predict with its
+ *                       "no neighbour -> 0" rule (knn3.cpp:216) when w_min = 0.1
+ * Everything after the score is cf_mf_topn's / cf_mf_rank_eval's contract, unchanged: candidates,
+ * exclusions (excl_*), NaN scores (a NaN rating is no error: its scores are NaN, counted and never
+ * listed), -0 as +0, the order, N <= CF_TOPN_MAX_N, sel_user, the user blocks (cf_set_topn_block),
+ * outputs, tails, stats structs, the held_* rules, the m = 0 user rule and the host-side metric
+ * orders.  The summation order is fixed, so a user's outputs are the same bytes across repeats, for
+ * every user-block size, for either graph layout and whichever other users are selected; there is
+ * no floating-point atomic.  score_ms counts the scoring kernel and, when the call builds them, the
+ * graph's in-lists (cached in the context per w_min until the next graph upload).
+ * CF_ESTATE: no graph uploaded.  CF_EINVAL: an unknown score_mode, a w_min that is not finite and
+ * >= 0, N == 0, a prof_off that is NULL, does not start at 0 or decreases, a prof_item >= n_items,
+ * and every exclusion, selection or held-out error of the mf calls.  CF_ERANGE: N > CF_TOPN_MAX_N, a
+ * graph of more than 2^24 items.
+ * Calls with no users, no selected users or no held-out edges succeed and write zeros as the mf
+ * calls do. */
+#define CF_KNN_SCORE_SUM 0
+#define CF_KNN_SCORE_MEAN 1
+int cf_knn_topn(cf_ctx* ctx, uint32_t n_users, const uint64_t* prof_off, const uint32_t* prof_item,
+                const float* prof_rating, int score_mode, double w_min, const uint64_t* excl_off,
+                const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user, uint32_t N, uint32_t* items,
+                double* scores, uint32_t* count, cf_topn_stats* stats);
+int cf_knn_rank_eval(cf_ctx* ctx, uint32_t n_users, const uint64_t* prof_off, const uint32_t* prof_item,
+                     const float* prof_rating, int score_mode, double w_min, const uint64_t* excl_off,
+                     const uint32_t* excl_item, const uint64_t* held_off, const uint32_t* held_item,
+                     const double* held_w, uint32_t N, uint32_t* rank, cf_rank_user* users, cf_rank_summary* summary);
+/* In-list entries per trip of the scoring kernel's walk (threads x entries in flight per lane): a
+ * constant of cf_knn_topn.hip; test helper. */
+int cf_debug_knn_topn_walk(void);
 
 /* ---- implicit-feedback ALS (Hu, Koren, Volinsky, ICDM 2008; no reference counterpart: wals.cpp
  * cites the paper and fits observed and sampled edges only) ----
