@@ -19,6 +19,9 @@ CF_ERANGE = -4
 CF_ESTATE = -5
 CF_KNN_SCORE_SUM = 0
 CF_KNN_SCORE_MEAN = 1
+CF_NMF_OBSERVED = 0
+CF_NMF_GRID = 1
+CF_NMF_EPS = 1e-16
 CF_SVD_MAX_NV = 256
 CF_ALS_MAX_D = 64
 CF_TOPN_MAX_N = 1024
@@ -173,6 +176,10 @@ SIGNATURES = {
     "cf_ials_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 13),
     "cf_mf_gram": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "cf_debug_ials_gram_rows": (c_int, []),
+    "cf_nmf_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 6 + [c_int, c_uint32] + [c_void_p] * 4),
+    "cf_nmf_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 6 + [c_int] + [c_void_p] * 3),
+    "cf_mf_colsum": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "cf_debug_nmf_sum_rows": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }
@@ -200,6 +207,12 @@ class AlsStats(ctypes.Structure):
 class IalsStats(ctypes.Structure):
     """cf_ials_stats (cf_abi.h)."""
     _fields_ = [("sweeps", c_uint32), ("n_not_pd", c_uint64), ("gram_ms", c_float), ("update_ms", c_float),
+                ("loss_ms", c_float)]
+
+
+class NmfStats(ctypes.Structure):
+    """cf_nmf_stats (cf_abi.h)."""
+    _fields_ = [("sweeps", c_uint32), ("n_floored", c_uint64), ("sum_ms", c_float), ("update_ms", c_float),
                 ("loss_ms", c_float)]
 
 

@@ -94,6 +94,21 @@ class IalsResult:
 
 
 @dataclass
+class NmfResult:
+    """Outcome of Context.nmf_fit: fitted factors, the loss after each half-sweep (2 * n_sweeps
+    values) and the cf_nmf_stats of the run."""
+
+    U: np.ndarray
+    V: np.ndarray
+    loss_trace: np.ndarray
+    sweeps: int
+    n_floored: int
+    sum_ms: float
+    update_ms: float
+    loss_ms: float
+
+
+@dataclass
 class SgdResult:
     """Outcome of Context.sgd_fit: fitted factors and biases (None for plain SGD), per-vertex
     update counts, the trace (one row {sum sq err TRAIN, sum sq err VALIDATE} per user
@@ -827,6 +842,52 @@ class Context:
         self._chk(self.lib.cf_mf_gram(self.h, F.shape[0], F.shape[1], ptr(F), ptr(G)), "cf_mf_gram")
         return G
 
+    # -- KL-divergence NMF, observed pairs or the whole grid ----------------------------------
+    def _nmf_graph(self, user, item, obs, n_users, n_items, mode):
+        """The two CSRs as cf_nmf_* take them and the mode constant."""
+        modes = {"observed": _native.CF_NMF_OBSERVED, "grid": _native.CF_NMF_GRID}
+        if mode not in modes:
+            raise ValueError('mode must be "grid" or "observed"')
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        return _mf_csr_pair(user, item, obs, n_users, n_items), modes[mode]
+
+    def nmf_fit(self, user, item, obs, n_users, n_items, U0, V0, *, mode="grid", n_sweeps=10, trace=True) -> "NmfResult":
+        """cf_nmf_fit: n_sweeps sweeps of the multiplicative KL-divergence updates over the edges
+        (user[e], item[e], obs[e] >= 0) from positive initial factors (every component >=
+        CF_NMF_EPS).  mode="observed" fits the rated pairs only; mode="grid" fits every pair of the
+        n_users x n_items grid with the unrated ones equal to 0.  trace=False skips the loss
+        evaluations."""
+        n_users, n_items, n_sweeps = int(n_users), int(n_items), int(n_sweeps)
+        (U, V), D = _mf_factors((U0, V0), (n_users, n_items), "U0 and V0", "U0 / V0")
+        g, m = self._nmf_graph(user, item, obs, n_users, n_items, mode)
+        loss = np.zeros(2 * n_sweeps, dtype=np.float64) if trace else None
+        st = _native.NmfStats()
+        self._chk(self.lib.cf_nmf_fit(self.h, n_users, n_items, int(D), *[ptr(x) for x in g], m, n_sweeps, ptr(U), ptr(V),
+                                      ptr(loss), byref(st)), "cf_nmf_fit")
+        return NmfResult(U, V, loss if trace else np.zeros(0), int(st.sweeps), int(st.n_floored), float(st.sum_ms),
+                         float(st.update_ms), float(st.loss_ms))
+
+    def nmf_loss(self, user, item, obs, n_users, n_items, U, V, *, mode="grid") -> float:
+        """cf_nmf_loss: the generalised KL loss of any positive factors, in either mode."""
+        n_users, n_items = int(n_users), int(n_items)
+        (U, V), D = _mf_factors((U, V), (n_users, n_items), "U and V", "U / V")
+        g, m = self._nmf_graph(user, item, obs, n_users, n_items, mode)
+        out = c_double()
+        self._chk(self.lib.cf_nmf_loss(self.h, n_users, n_items, int(D), *[ptr(x) for x in g], m, ptr(U), ptr(V),
+                                       byref(out)), "cf_nmf_loss")
+        return out.value
+
+    def mf_colsum(self, F) -> np.ndarray:
+        """cf_mf_colsum: the column sums (D) of an n x D matrix, summed in slices of fixed length."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.ndim != 2 or F.shape[1] == 0:
+            raise ValueError("F must be n x D with D >= 1")
+        s = np.zeros(F.shape[1], dtype=np.float64)
+        self._chk(self.lib.cf_mf_colsum(self.h, F.shape[0], F.shape[1], ptr(F), ptr(s)), "cf_mf_colsum")
+        return s
+
     # -- SGD / bias-SGD matrix factorization (sgd.cpp, biassgd.cpp) ----------------------
     def sgd_fit(self, user, item, obs, n_users, n_items, U0, V0, *, bias=False, lam=0.001, gamma=0.001, step_dec=0.9,
                 tol=1e-3, minval=-1e100, maxval=1e100, global_mean=None, bias_user=None, bias_item=None,
@@ -1388,6 +1449,6 @@ class Plan:
                   ptr(d_pred), c_void_p(stream or 0)), "cf_predict_run")
 
 
-__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "SgdResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
+__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "SgdResult", "NmfResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
            "predict_precomp_multi", "CF_SIGS_OWN", "CF_SIGS_COMPAT", "CF_FILTER_CHEBY",
            "CF_FILTER_BINOMIAL"]

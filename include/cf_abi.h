@@ -953,6 +953,59 @@ int cf_mf_gram(cf_ctx* ctx, uint32_t n, uint32_t D, const double* F, double* G);
 /* The slice length of the global Gram (a constant of cf_ials.hip; test helper, needs no GPU). */
 int cf_debug_ials_gram_rows(void);
 
+/* ---- non-negative matrix factorization under the generalised Kullback-Leibler divergence (Lee and
+ * Seung's multiplicative rules).  nmf.cpp sums the rule's numerator over every edge of the graph
+ * into one vector for all vertices, which is no factorization; these entry points fit what its
+ * header and its pre_iter column sum stand for ----
+ * R ~ U V^T, every component >= CF_NMF_EPS.  For an edge (u, i, r), r >= 0 (f32; repeated edges each
+ * count), p = U_u.V_i, with 0 log 0 = 0:
+ *   CF_NMF_OBSERVED  L = sum_edges [r log(r / p) - r + p]
+ *                    U_u[d] <- U_u[d] (sum_{e in N(u)} V_i[d] r / p) / (sum_{e in N(u)} V_i[d])
+ *   CF_NMF_GRID      L = sum_edges [r log(r / p) - r] + s_U.s_V,  s_F[d] = sum over ALL rows of F[.][d]
+ *                    (every pair of the grid counts, unrated = 0: Poisson factorization)
+ *                    U_u[d] <- U_u[d] (sum_{e in N(u)} V_i[d] r / p) / s_V[d]
+ * and a component below CF_NMF_EPS becomes CF_NMF_EPS (n_floored counts these).  A sweep is the user
+ * half-sweep from the current V, then the item half-sweep from the new U; every value is read as
+ * it was at the start of the half-sweep.  An edge with r = 0 adds nothing to a numerator, adds its
+ * row to an OBSERVED denominator, and has loss term p (OBSERVED) or 0 (GRID).  A vertex without
+ * edges keeps its row bit for bit (OBSERVED) or becomes CF_NMF_EPS in every component (GRID; its
+ * row still counts in s_F).
+ * fp64 throughout and no floating-point atomics: a vertex's new row depends only on its own edge
+ * list, the other side's rows and, in GRID mode, the bits of s; a repeated fit gives the same bytes.
+ *   user_off / user_item / user_obs : CSR over users; item_* : its transpose (checked like
+ *       cf_als_fit's).  CF_EINVAL: an unknown mode, an obs that is negative or not finite, an initial
+ *       factor component that is not finite or below CF_NMF_EPS (a zero never leaves zero)
+ *   U [n_users * D], V [n_items * D] : in the initial factors, out the fitted ones
+ *   loss_trace : NULL, or 2 * n_sweeps doubles: L after each half-sweep, the same bits as
+ *       cf_nmf_loss of the factors at that point
+ * D == 0 gives CF_EINVAL, D > CF_ALS_MAX_D CF_ERANGE; n_sweeps == 0 (U, V untouched), no edges and an
+ * empty side are valid calls. */
+#define CF_NMF_OBSERVED 0
+#define CF_NMF_GRID 1
+#define CF_NMF_EPS 1e-16
+typedef struct cf_nmf_stats {
+    uint32_t sweeps;       /* sweeps run */
+    uint64_t n_floored;    /* components set to CF_NMF_EPS, over the whole fit */
+    float sum_ms;          /* device time of the column-sum kernels before the half-sweeps (HIP events) */
+    float update_ms;       /* device time of the per-vertex update kernels */
+    float loss_ms;         /* device time of the loss kernels (0 without a trace) */
+} cf_nmf_stats;
+int cf_nmf_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+               const uint32_t* user_item, const float* user_obs, const uint64_t* item_off, const uint32_t* item_user,
+               const float* item_obs, int mode, uint32_t n_sweeps, double* U, double* V, double* loss_trace,
+               cf_nmf_stats* stats);
+/* *loss = L(U, V) of any factors that pass cf_nmf_fit's checks.  Fixed reductions: the same inputs
+ * give the same bits. */
+int cf_nmf_loss(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+                const uint32_t* user_item, const float* user_obs, const uint64_t* item_off, const uint32_t* item_user,
+                const float* item_obs, int mode, const double* U, const double* V, double* loss);
+/* s [D] = the column sums of the n x D row-major matrix F: slices of cf_debug_nmf_sum_rows() rows,
+ * summed in slice order; a slice's partial depends on its own rows only.  The same bits in every
+ * run; appending rows that are all zero does not change it.  n == 0 gives zeros. */
+int cf_mf_colsum(cf_ctx* ctx, uint32_t n, uint32_t D, const double* F, double* s);
+/* The slice length of the column sum (a constant of cf_nmf.hip; test helper, needs no GPU). */
+int cf_debug_nmf_sum_rows(void);
+
 #ifdef __cplusplus
 }
 #endif
