@@ -22,6 +22,7 @@ CF_KNN_SCORE_MEAN = 1
 CF_NMF_OBSERVED = 0
 CF_NMF_GRID = 1
 CF_NMF_EPS = 1e-16
+CF_BPR_TRIES = 8
 CF_SVD_MAX_NV = 256
 CF_ALS_MAX_D = 64
 CF_TOPN_MAX_N = 1024
@@ -180,6 +181,10 @@ SIGNATURES = {
     "cf_nmf_loss": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 6 + [c_int] + [c_void_p] * 3),
     "cf_mf_colsum": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "cf_debug_nmf_sum_rows": (c_int, []),
+    "cf_bpr_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32] + [c_void_p] * 10),
+    "cf_bpr_sample": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "cf_bpr_timing": (c_int, [c_void_p, c_void_p]),
+    "cf_debug_bpr_tries": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }
@@ -214,6 +219,18 @@ class NmfStats(ctypes.Structure):
     """cf_nmf_stats (cf_abi.h)."""
     _fields_ = [("sweeps", c_uint32), ("n_floored", c_uint64), ("sum_ms", c_float), ("update_ms", c_float),
                 ("loss_ms", c_float)]
+
+
+class BprParams(ctypes.Structure):
+    """cf_bpr_params (cf_abi.h)."""
+    _fields_ = [("lr", c_double), ("reg_user", c_double), ("reg_item", c_double), ("reg_bias", c_double),
+                ("seed", c_uint64), ("first_sweep", c_uint32), ("n_sweeps", c_uint32)]
+
+
+class BprStats(ctypes.Structure):
+    """cf_bpr_stats (cf_abi.h)."""
+    _fields_ = [("sweeps", c_uint32), ("triples", c_uint64), ("n_skipped", c_uint64), ("n_nan", c_uint64),
+                ("sample_ms", c_float), ("reduce_ms", c_float), ("apply_ms", c_float)]
 
 
 class SgdParams(ctypes.Structure):

@@ -109,6 +109,27 @@ class NmfResult:
 
 
 @dataclass
+class BprResult:
+    """Outcome of Context.bpr_fit: fitted factors, the item biases (None without), the trace (one
+    row {sum of softplus(-x), triples} per sweep run; empty without) and the cf_bpr_stats of the
+    run; stage_ms is cf_bpr_timing: sample, negative lists, user / item positive / item negative
+    reduction, commit."""
+
+    U: np.ndarray
+    V: np.ndarray
+    bias_item: np.ndarray | None
+    loss_trace: np.ndarray
+    sweeps: int
+    triples: int
+    n_skipped: int
+    n_nan: int
+    sample_ms: float
+    reduce_ms: float
+    apply_ms: float
+    stage_ms: np.ndarray
+
+
+@dataclass
 class SgdResult:
     """Outcome of Context.sgd_fit: fitted factors and biases (None for plain SGD), per-vertex
     update counts, the trace (one row {sum sq err TRAIN, sum sq err VALIDATE} per user
@@ -888,6 +909,64 @@ class Context:
         self._chk(self.lib.cf_mf_colsum(self.h, F.shape[0], F.shape[1], ptr(F), ptr(s)), "cf_mf_colsum")
         return s
 
+    # -- Bayesian Personalized Ranking (no reference counterpart) -----------------------------
+    @staticmethod
+    def _bpr_graph(user, item, n_users, n_items):
+        """The positive pairs sorted by (user, item) as the user CSR and its transpose:
+        (user_off, user_item, item_off, item_user).  A repeated pair raises ValueError."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        if len(user) != len(item):
+            raise ValueError("user and item differ in length")
+        if len(user) and (int(user.max()) >= n_users or int(item.max()) >= n_items):
+            raise ValueError("edge index out of range")
+        p = np.lexsort((item, user))
+        user, item = user[p], item[p]
+        if len(user) > 1 and bool(np.any((user[1:] == user[:-1]) & (item[1:] == item[:-1]))):
+            raise ValueError("a positive pair appears twice")
+        none = np.zeros(len(user), np.float32)
+        uoff, uitem, _ = _csr(user, item, none, n_users)
+        ioff, iuser, _ = _csr(item, user, none, n_items)   # stable: users ascend within an item
+        return uoff, uitem, ioff, iuser
+
+    def bpr_fit(self, user, item, n_users, n_items, U0, V0, *, bias0=None, lr=0.05, reg_user=0.01, reg_item=0.01,
+                reg_bias=0.01, n_sweeps=10, seed=0, first_sweep=0, trace=True) -> "BprResult":
+        """cf_bpr_fit: n_sweeps Jacobi sweeps of BPR over the positive pairs (user[e], item[e]), one
+        sampled negative per pair and sweep (cf_abi.h has the rule).  bias0: initial item biases,
+        None for a model without.  first_sweep continues an earlier fit: its sweeps draw the
+        negatives of sweep indices first_sweep, first_sweep + 1, ..  The pairs may come in any
+        order; a repeated pair raises ValueError."""
+        n_users, n_items, n_sweeps = int(n_users), int(n_items), int(n_sweeps)
+        (U, V), D = _mf_factors((U0, V0), (n_users, n_items), "U0 and V0", "U0 / V0")
+        b = None if bias0 is None else np.array(bias0, dtype=np.float64, order="C").reshape(-1)
+        if b is not None and len(b) != n_items:
+            raise ValueError("bias0 does not hold one value per item")
+        if b is not None and not len(b):
+            b = np.zeros(1)   # a valid pointer: the model has a bias
+        g = self._bpr_graph(user, item, n_users, n_items)
+        loss = np.zeros(2 * n_sweeps, dtype=np.float64) if trace else None
+        par = _native.BprParams(float(lr), float(reg_user), float(reg_item), float(reg_bias), int(seed), int(first_sweep),
+                                n_sweeps)
+        st = _native.BprStats()
+        self._chk(self.lib.cf_bpr_fit(self.h, n_users, n_items, int(D), *[ptr(x) for x in g], byref(par), ptr(U), ptr(V),
+                                      ptr(b), ptr(loss), byref(st)), "cf_bpr_fit")
+        ms = np.zeros(6, dtype=np.float32)
+        self._chk(self.lib.cf_bpr_timing(self.h, ptr(ms)), "cf_bpr_timing")
+        tr = loss.reshape(n_sweeps, 2)[: int(st.sweeps)] if trace else np.zeros((0, 2))
+        return BprResult(U, V, None if b is None else b[:n_items], tr, int(st.sweeps), int(st.triples), int(st.n_skipped),
+                         int(st.n_nan), float(st.sample_ms), float(st.reduce_ms), float(st.apply_ms), ms)
+
+    def bpr_sample(self, user, item, n_users, n_items, *, seed=0, sweep=0):
+        """cf_bpr_sample: (neg, n_skipped) with neg[p] the negative item of the p-th positive pair in
+        (user, item) order for that seed and sweep index, 0xFFFFFFFF where the pair is skipped."""
+        n_users, n_items = int(n_users), int(n_items)
+        uoff, uitem, _, _ = self._bpr_graph(user, item, n_users, n_items)
+        neg = np.full(max(len(uitem), 1), 0xFFFFFFFF, dtype=np.uint32)
+        skipped = _native.c_uint64()
+        self._chk(self.lib.cf_bpr_sample(self.h, n_users, n_items, ptr(uoff), ptr(uitem), int(seed), int(sweep), ptr(neg),
+                                         byref(skipped)), "cf_bpr_sample")
+        return neg[: len(uitem)], int(skipped.value)
+
     # -- SGD / bias-SGD matrix factorization (sgd.cpp, biassgd.cpp) ----------------------
     def sgd_fit(self, user, item, obs, n_users, n_items, U0, V0, *, bias=False, lam=0.001, gamma=0.001, step_dec=0.9,
                 tol=1e-3, minval=-1e100, maxval=1e100, global_mean=None, bias_user=None, bias_item=None,
@@ -1449,6 +1528,6 @@ class Plan:
                   ptr(d_pred), c_void_p(stream or 0)), "cf_predict_run")
 
 
-__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "SgdResult", "NmfResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
+__all__ = ["Context", "Plan", "EigenResult", "AlsResult", "SgdResult", "NmfResult", "BprResult", "evec_offsets", "cost_split_native", "eigen_batch_multi",
            "predict_precomp_multi", "CF_SIGS_OWN", "CF_SIGS_COMPAT", "CF_FILTER_CHEBY",
            "CF_FILTER_BINOMIAL"]

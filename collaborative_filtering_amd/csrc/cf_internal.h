@@ -180,6 +180,8 @@ struct cf_ctx {
     // SVD++ (cf_svdpp_timing): the same of the last cf_svdpp_fit per kernel kind: phase-1 user
     // reduction, phase-2 user reduction, item message reduction
     float svdpp_reduce_ms[3] = {0.0f, 0.0f, 0.0f};
+    // BPR (cf_bpr_timing): the last cf_bpr_fit's device times by stage
+    float bpr_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     // top-N (cf_topn.hip): users per block forced by cf_set_topn_block (0 = from the byte budget)
     uint32_t topn_block = 0;
     // item-kNN top-N (cf_knn_topn.hip): the in-lists of the resident graph above knn_in_wmin, a

@@ -31,33 +31,9 @@
 #include <rocprim/rocprim.hpp>
 
 #include "cf_internal.h"
+#include "cf_sort.h"   // SortCfg, sort_pairs, sort_keys, bits_for: the stable merge-sort path
 
 namespace {
-
-// Sorts run rocprim's stable merge-sort path at every size (radix_sort_config with an unbounded
-// merge-sort limit).  Inside a PyTorch process this library is served by torch's bundled HIP
-// runtime, under which rocprim's onesweep radix path fails to launch (hipErrorInvalidValue, in
-// both its gfx950-tuned and generic configurations), while the merge path runs; standalone on
-// the ROCm 7.2 runtime all of them run (tools/probe_sort.hip, 10.7M u64 keys + u32 values,
-// 47 bits: onesweep 0.94 ms, merge sort 0.86 ms).
-using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config,
-                                           (size_t)1 << 40>;
-
-template <class K, class V>
-hipError_t sort_pairs(void* tmp, size_t& bytes, const K* ki, K* ko, const V* vi, V* vo, uint64_t n, int bits,
-                      hipStream_t st) {
-    return rocprim::radix_sort_pairs<SortCfg>(tmp, bytes, ki, ko, vi, vo, (unsigned int)n, 0u, (unsigned int)bits, st);
-}
-template <class K>
-hipError_t sort_keys(void* tmp, size_t& bytes, const K* ki, K* ko, uint64_t n, int bits, hipStream_t st) {
-    return rocprim::radix_sort_keys<SortCfg>(tmp, bytes, ki, ko, (unsigned int)n, 0u, (unsigned int)bits, st);
-}
-
-inline int bits_for(uint64_t n) {   // bits to represent 0 .. n-1 (>= 1)
-    int b = 1;
-    while (b < 64 && (1ull << b) < n) ++b;
-    return b;
-}
 
 __global__ void regroup_keys_kernel(uint64_t n, const uint32_t* user, const uint32_t* movie, const uint8_t* role,
                                     uint32_t n_movies, uint64_t* key, uint32_t* idx) {

@@ -1006,6 +1006,74 @@ int cf_mf_colsum(cf_ctx* ctx, uint32_t n, uint32_t D, const double* F, double* s
 /* The slice length of the column sum (a constant of cf_nmf.hip; test helper, needs no GPU). */
 int cf_debug_nmf_sum_rows(void);
 
+/* ---- Bayesian Personalized Ranking (Rendle et al., UAI 2009): matrix factorization trained on the
+ * pairwise objective  sum ln sigmoid(x_ui - x_uj)  over (user, rated item, unrated item) triples, the
+ * smooth form of the AUC cf_mf_rank_eval reports.  No reference counterpart ----
+ * Inputs: the positive pairs as the user CSR user_off / user_item and its transpose item_off /
+ * item_user.  There are no ratings: an edge is a positive.  Both sides' lists are STRICTLY ASCENDING
+ * (an edge cannot appear twice and membership is a binary search); anything else, and CSRs that are
+ * not each other's transpose, give CF_EINVAL.  State in fp64: U [n_users x D], V [n_items x D] and
+ * the optional bias_item [n_items] (NULL: no bias, every b below is 0 and none is written).
+ * Score: x_ui = U_u . V_i + b_i.
+ *
+ * The sample is integers only; nothing about it depends on a factor.  sm is splitmix64 with the
+ * final x ^ (x >> 31) (host/cf_mf_cli.hpp), T = CF_BPR_TRIES.  For sweep index s, user u and the
+ * edge at rank r of u's list (its item is i):
+ *     key_s   = sm(sm(seed) ^ s)
+ *     h(t)    = sm(sm(key_s ^ u) ^ (r * T + t))            t = 0 .. T-1
+ *     cand(t) = (uint32)(((h(t) >> 32) * n_items) >> 32)
+ *     j       = the first cand(t) that is not in u's list
+ * If all T candidates are in the list the edge is SKIPPED this sweep: it has no triple, adds nothing
+ * anywhere, and counts in n_skipped.  A user's negatives depend on seed, s, u and its own list only.
+ *
+ * A sweep (a Jacobi step: every value is read as it was at the start of the sweep).  Per triple
+ *     x = U_u . (V_i - V_j) + b_i - b_j,    g = 1 / (1 + exp(x))
+ * and with c_u the number of triples of user u, c_i the number of triples in which item i is the
+ * positive PLUS the number in which it is the negative:
+ *     U_u += lr ((sum_{triples of u} g (V_i - V_j)) / c_u - reg_user U_u)                      c_u > 0
+ *     V_i += lr ((sum_{i positive} g U_u - sum_{i negative} g U_u) / c_i - reg_item V_i)       c_i > 0
+ *     b_i += lr ((sum_{i positive} g     - sum_{i negative} g    ) / c_i - reg_bias b_i)       c_i > 0
+ * A vertex with count 0 keeps its row bit for bit.  The division by the vertex's own count keeps the
+ * stationary points of per-triple regularised BPR-OPT and bounds a vertex's step by lr whatever its
+ * degree.
+ *   loss_trace : NULL, or 2 * n_sweeps doubles; row s = {sum over the sweep's triples of
+ *       softplus(-x), (double) number of triples}, from the start-of-sweep factors, by a fixed
+ *       two-level reduction
+ *   a NaN x counts in n_nan, and the fit ends after a sweep with n_nan > 0 (stats->sweeps tells)
+ *   params->first_sweep : the index s of the first sweep; n_sweeps = 5 gives the same bytes as
+ *       n_sweeps = 2 followed by first_sweep = 2, n_sweeps = 3 on its results
+ * Determinism: a vertex's class, split points and every summation order depend on the
+ * length of the list being summed only; no floating-point atomic; a repeated fit gives the same
+ * bytes; a user's new row depends on its own list and the item rows only.
+ * D == 0 gives CF_EINVAL, D > CF_ALS_MAX_D CF_ERANGE; lr or a reg that is not finite, or a negative
+ * reg, CF_EINVAL; n_sweeps == 0 (factors untouched), no edges and an empty side are valid calls. */
+#define CF_BPR_TRIES 8
+typedef struct cf_bpr_params {
+    double lr, reg_user, reg_item, reg_bias;
+    uint64_t seed;
+    uint32_t first_sweep, n_sweeps;
+} cf_bpr_params;
+typedef struct cf_bpr_stats {
+    uint32_t sweeps;                       /* sweeps run */
+    uint64_t triples, n_skipped, n_nan;    /* over those sweeps */
+    float sample_ms, reduce_ms, apply_ms;  /* HIP-event device times: sample and gradient kernel; the
+                                              negative lists and the three reductions; the commits */
+} cf_bpr_stats;
+int cf_bpr_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint32_t D, const uint64_t* user_off,
+               const uint32_t* user_item, const uint64_t* item_off, const uint32_t* item_user,
+               const cf_bpr_params* params, double* U, double* V, double* bias_item, double* loss_trace,
+               cf_bpr_stats* stats);
+/* The sampler alone: neg[p] for every position p of the user CSR, UINT32_MAX = skipped; *n_skipped
+ * (may be NULL) counts those.  The lists are checked as cf_bpr_fit checks them. */
+int cf_bpr_sample(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t* user_off, const uint32_t* user_item,
+                  uint64_t seed, uint32_t sweep, uint32_t* neg, uint64_t* n_skipped);
+/* Device times of the last cf_bpr_fit, summed over its sweeps: {sample and gradient, sort + offsets +
+ * class lists of the negative CSR, user reduction, item positive reduction, item negative
+ * reduction, commit}. */
+int cf_bpr_timing(cf_ctx* ctx, float ms[6]);
+/* CF_BPR_TRIES as compiled (test helper, needs no GPU). */
+int cf_debug_bpr_tries(void);
+
 #ifdef __cplusplus
 }
 #endif
