@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import cf_prep_oracle as prep
+from prep_cases import assert_regroup_equal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "fold_cases.npz"))
@@ -110,15 +111,7 @@ def regroup_case(seed, n_users, n_movies, n, dup_frac=0.1, val_frac=0.3):
 def test_knn_regroup_matches_restatement(gpu_ctx, seed, n_users, n_movies, n):
     user, movie, rating, validate = regroup_case(seed, n_users, n_movies, n)
     g = gpu_ctx.knn_regroup(n_users, n_movies, user, movie, rating, validate)
-    train, test, corated = prep.knn_regroup(n_movies, user, movie, rating, validate)
-    for m in range(n_movies):
-        for kind, ref in (("train", train[m]), ("test", test[m])):
-            off = g[kind + "_off"]
-            us = g[kind + "_user"][off[m]:off[m + 1]].tolist()
-            rs = g[kind + "_rating"][off[m]:off[m + 1]].tolist()
-            assert us == sorted(ref) and rs == [ref[u] for u in sorted(ref)], (kind, m)
-        eo = g["edg_off"]
-        assert g["edg_movie"][eo[m]:eo[m + 1]].tolist() == corated[m], m
+    assert_regroup_equal(g, prep.knn_regroup(n_movies, user, movie, rating, validate))
 
 
 @pytest.mark.gpu
