@@ -185,6 +185,20 @@ SIGNATURES = {
     "cf_bpr_sample": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
     "cf_bpr_timing": (c_int, [c_void_p, c_void_p]),
     "cf_debug_bpr_tries": (c_int, []),
+    "cf_ease_fit": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_double]),
+    "cf_ease_gram": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p]),
+    "cf_ease_weights": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cf_ease_upload": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "cf_ease_topn": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_uint32,
+                             c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_ease_rank_eval": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "cf_ease_timing": (c_int, [c_void_p, c_void_p]),
+    "cf_debug_ease_inverse": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                      c_void_p]),
+    "cf_debug_ease_block": (c_int, []),
+    "cf_debug_ease_cols": (c_int, []),
+    "cf_debug_ease_unroll": (c_int, []),
     "cf_eigen_batch_stream": (c_int, [c_void_p, c_int, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p,
                                       c_void_p]),
 }

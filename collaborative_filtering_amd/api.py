@@ -1266,6 +1266,109 @@ class Context:
                                             byref(st)), "cf_knn_rank_eval")
         return _rank_result(su, perm, rank, users[:n_users], st)
 
+    # -- EASE: the closed-form item-item model (no reference counterpart) --------------
+    @staticmethod
+    def _ease_train(user_off, items, ratings):
+        """The TRAIN edges of a fit as (n_users, off, items, ratings)."""
+        off = np.ascontiguousarray(user_off, dtype=np.uint64)
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        rat = np.ascontiguousarray(ratings, dtype=np.float32)
+        if len(off) < 1 or len(it) != len(rat) or int(off[-1]) != len(it):
+            raise ValueError("user_off / items / ratings do not describe one TRAIN CSR")
+        if not len(it):   # valid pointers for an empty edge list
+            it, rat = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        return len(off) - 1, off, it, rat
+
+    def ease_fit(self, user_off, items, ratings, n_items, lam, *, binary=False) -> np.ndarray:
+        """cf_ease_fit: G = X^T X + lam I, P = G^-1, B = -P / diag(P) with a zero diagonal, from
+        the TRAIN edges as a CSR by user (item lists strictly ascending; the value of an edge is 1
+        when `binary`, else its rating).  B stays resident in the context for ease_topn /
+        ease_rank_eval / ease_weights.  Returns ease_timing()."""
+        n_users, off, it, rat = self._ease_train(user_off, items, ratings)
+        self._chk(self.lib.cf_ease_fit(self.h, n_users, int(n_items), ptr(off), ptr(it), ptr(rat), int(bool(binary)),
+                                       float(lam)), "cf_ease_fit")
+        return self.ease_timing()
+
+    def ease_gram(self, user_off, items, ratings, n_items, lam, *, binary=False) -> np.ndarray:
+        """cf_ease_gram: the fit's Gram stage alone, G [n_items, n_items] in float64."""
+        n_users, off, it, rat = self._ease_train(user_off, items, ratings)
+        G = np.zeros((int(n_items), int(n_items)), dtype=np.float64)
+        self._chk(self.lib.cf_ease_gram(self.h, n_users, int(n_items), ptr(off), ptr(it), ptr(rat), int(bool(binary)),
+                                        float(lam), ptr(G) if G.size else None), "cf_ease_gram")
+        return G
+
+    def ease_inverse(self, user_off, items, ratings, n_items, lam, *, binary=False) -> np.ndarray:
+        """cf_debug_ease_inverse: P = G^-1 as the fit computes it, before the normalisation (the
+        resident B is left as it is)."""
+        n_users, off, it, rat = self._ease_train(user_off, items, ratings)
+        P = np.zeros((int(n_items), int(n_items)), dtype=np.float64)
+        self._chk(self.lib.cf_debug_ease_inverse(self.h, n_users, int(n_items), ptr(off), ptr(it), ptr(rat),
+                                                 int(bool(binary)), float(lam), ptr(P) if P.size else None),
+                  "cf_debug_ease_inverse")
+        return P
+
+    def ease_weights(self) -> np.ndarray:
+        """cf_ease_weights: the resident B [n_items, n_items] in float64."""
+        n = c_uint32(0)
+        self._chk(self.lib.cf_ease_weights(self.h, byref(n), None), "cf_ease_weights")
+        B = np.zeros((int(n.value), int(n.value)), dtype=np.float64)
+        self._chk(self.lib.cf_ease_weights(self.h, byref(n), ptr(B)), "cf_ease_weights")
+        return B
+
+    def ease_upload(self, B):
+        """cf_ease_upload: any square float64 B (signed, NaN allowed) as the resident weights."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != B.shape[1]:
+            raise ValueError("B must be n_items x n_items")
+        self._chk(self.lib.cf_ease_upload(self.h, B.shape[0], ptr(B) if B.size else None), "cf_ease_upload")
+
+    def ease_timing(self) -> np.ndarray:
+        """cf_ease_timing: device ms of the last ease_fit: Gram, inversion, normalisation."""
+        ms = np.zeros(3, dtype=np.float32)
+        self._chk(self.lib.cf_ease_timing(self.h, ptr(ms)), "cf_ease_timing")
+        return ms
+
+    def _ease_profile(self, user_off, items, ratings, exclude):
+        """The arguments cf_ease_topn and cf_ease_rank_eval share: those of the graph source but its mode."""
+        n_users, off, it, rat, _, eoff, eitem = self._knn_profile(user_off, items, ratings, "sum", exclude)
+        return n_users, off, it, rat, eoff, eitem
+
+    def ease_topn(self, user_off, items, ratings, N, *, binary=False, exclude="profile", users=None) -> "TopnResult":
+        """cf_ease_topn: for every user (or every user of `users`, in its order) the N best items by
+        s(u, j) = sum_t x_t B[i_t][j] over the user's profile (user_off / items / ratings, in the
+        order the sum runs; x = 1 when `binary`, else the rating) with the resident B.  The profile
+        need not be the fit's: any user can be scored.  exclude: "profile" (the user's own items),
+        None, or (user, item) arrays."""
+        n_users, off, it, rat, eoff, eitem = self._ease_profile(user_off, items, ratings, exclude)
+        N = int(N)
+        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
+        n_out = n_users if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.uint32)
+        out_items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
+        count = np.zeros(n_out, dtype=np.uint32)
+        st = _native.TopnStats()
+        self._chk(self.lib.cf_ease_topn(self.h, n_users, ptr(off), ptr(it), ptr(rat), int(bool(binary)), ptr(eoff),
+                                        ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(out_items),
+                                        ptr(scores), ptr(count), byref(st)), "cf_ease_topn")
+        return TopnResult(out_items, scores, count, st)
+
+    def ease_rank_eval(self, user_off, items, ratings, N, held, *, binary=False, exclude="profile",
+                       weights=None) -> "RankEvalResult":
+        """cf_ease_rank_eval: mf_rank_eval with the scores of ease_topn.  held: (user, item) arrays of
+        the pairs to find, in any order; weights: one per held pair (mpr only)."""
+        n_users, off, it, rat, eoff, eitem = self._ease_profile(user_off, items, ratings, exclude)
+        N = int(N)
+        su, perm, hoff, hitem, hws = _held_csr((held[0], held[1], weights), n_users)
+        rank = np.zeros(max(len(su), 1), dtype=np.uint32)
+        users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
+        st = _native.RankSummary()
+        self._chk(self.lib.cf_ease_rank_eval(self.h, n_users, ptr(off), ptr(it), ptr(rat), int(bool(binary)), ptr(eoff),
+                                             ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank), ptr(users),
+                                             byref(st)), "cf_ease_rank_eval")
+        return _rank_result(su, perm, rank, users[:n_users], st)
+
     # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
     @staticmethod
     def svd_entries(row, col, val, rows, cols, regularization=0.0):

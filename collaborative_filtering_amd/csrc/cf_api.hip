@@ -149,6 +149,7 @@ void cf_destroy(cf_ctx* ctx) {
     if (ctx->d_gcol) (void)hipFree(ctx->d_gcol);
     if (ctx->d_gw) (void)hipFree(ctx->d_gw);
     cf_knn_in_free(ctx);
+    cf_ease_free(ctx);
     if (ctx->d_stats) (void)hipFree(ctx->d_stats);
     if (ctx->d_dbg) (void)hipFree(ctx->d_dbg);
     if (ctx->d_phase) (void)hipFree(ctx->d_phase);

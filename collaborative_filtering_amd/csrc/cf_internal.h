@@ -194,7 +194,16 @@ struct cf_ctx {
     double knn_in_wmin = 0.0;
     uint64_t knn_in_gen = ~0ull;
     int knn_topn_wgs = -1;   // -1: not read yet (CF_KNN_TOPN_WGS); workgroups of knn_score_kernel per CU
+    // EASE (cf_ease.hip): the resident item-item weights B, ease_n x ease_n fp64 row-major, an
+    // allocation of its own (cf_ease_free: the next fit or upload and cf_destroy; not a workspace),
+    // and the last fit's device times {Gram, inversion, normalise}
+    double* d_ease_B = nullptr;
+    uint32_t ease_n = 0;
+    float ease_ms[3] = {0.0f, 0.0f, 0.0f};
 };
+
+// Frees the resident EASE weights (cf_ease.hip).
+void cf_ease_free(cf_ctx* ctx);
 
 // Frees the cached in-lists (cf_knn_topn.hip): every graph upload and cf_destroy.
 void cf_knn_in_free(cf_ctx* ctx);
@@ -213,8 +222,9 @@ struct PanelSource {
     // keys of rows [0, nb) of the panel (row stride n_items): the users sel[b0 + r], or b0 + r where sel is null
     virtual int fill(cf_ctx* ctx, hipStream_t st, const uint32_t* d_sel, uint32_t b0, uint32_t nb, uint64_t* d_panel) = 0;
 };
-// cf_mf_topn / cf_knn_topn after the checks of their own score source (cf_topn.hip), and
-// cf_mf_rank_eval / cf_knn_rank_eval likewise (cf_rank.hip); fn names the caller in messages.
+// cf_mf_topn / cf_knn_topn / cf_ease_topn after the checks of their own score source (cf_topn.hip),
+// and cf_mf_rank_eval / cf_knn_rank_eval / cf_ease_rank_eval likewise (cf_rank.hip); fn names the
+// caller in messages.
 int cf_topn_drive(cf_ctx* ctx, const char* fn, PanelSource& src, uint32_t n_users, uint32_t n_items,
                   const uint64_t* excl_off, const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user,
                   uint32_t N, uint32_t* items, double* scores, uint32_t* count, cf_topn_stats* stats);

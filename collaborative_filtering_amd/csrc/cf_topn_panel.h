@@ -2,7 +2,8 @@
 // (the rank of held-out items) share: the order-preserving 64-bit key of a score, the kernel that
 // scores a block of users into a panel of keys, the kernel that marks the excluded pairs in it, the
 // row walk's loads, the order of two (key, item) pairs, the users-per-block rule and the factor
-// source of the panel drivers (MfPanelSource; cf_knn_topn.hip has the graph source).
+// source of the panel drivers (MfPanelSource; cf_knn_topn.hip has the graph source, cf_ease.hip
+// the EASE one).
 //
 // The selected users run in blocks of `ub` users whose scores live in a panel of 64-bit keys,
 // key[user in block][item] (row stride n_items, carved from the context's ALS workspace):

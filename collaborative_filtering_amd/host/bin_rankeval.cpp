@@ -23,6 +23,7 @@
 #include "cf_factor_io.hpp"
 #include "cf_knn_cli.hpp"
 #include "cf_mf_cli.hpp"
+#include "cf_rank_cli.hpp"
 
 int main(int argc, char** argv) {
     const std::string factors = cfcli::opt(argc, argv, "factors", "");
@@ -89,27 +90,10 @@ int main(int argc, char** argv) {
     }
     cfmf::Csr excl = cfmf::build_csr(nu, eu, em, std::vector<float>(eu.size(), 0.0f));
     if (excl.nbr.empty()) excl.nbr.push_back(0);   // a valid pointer for an empty list
-    std::stable_sort(held.begin(), held.end(), [](const auto& a, const auto& b) {
-        return std::get<0>(a) != std::get<0>(b) ? std::get<0>(a) < std::get<0>(b) : std::get<1>(a) < std::get<1>(b);
-    });
-    std::vector<uint64_t> hoff((size_t)nu + 1, 0);
-    std::vector<uint32_t> hitem;
-    std::vector<double> hw;
-    for (size_t e = 0; e < held.size(); ++e) {
-        const uint32_t u = std::get<0>(held[e]), m = std::get<1>(held[e]);
-        if (e && u == std::get<0>(held[e - 1]) && m == std::get<1>(held[e - 1]))
-            cfcli::die("user " + std::to_string(uids.ids[u]) + " item " + std::to_string(mids.ids[m]) + " of " + matrix +
-                       " is a VALIDATE edge twice");
-        hoff[u + 1]++;
-        hitem.push_back(m);
-        hw.push_back((double)std::get<2>(held[e]));
-    }
-    for (uint32_t u = 0; u < nu; ++u) hoff[u + 1] += hoff[u];
-    const uint64_t n_held = hitem.size();
-    if (hitem.empty()) {
-        hitem.push_back(0);
-        hw.push_back(0.0);
-    }
+    const cfrank::Held h = cfrank::build_held(std::move(held), nu, uids, mids, matrix);
+    const std::vector<uint64_t>& hoff = h.off;
+    const std::vector<uint32_t>& hitem = h.item;
+    const std::vector<double>& hw = h.w;
 
     if (from_graph) std::printf("Users: %u items: %u\n", nu, nm);
     else std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
@@ -130,31 +114,8 @@ int main(int argc, char** argv) {
                                      hitem.data(), weighted ? hw.data() : nullptr, N, rank.data(), users.data(), &s),
                      "cf_mf_rank_eval");
     }
-    std::printf("Evaluated users: %u held-out edges: %llu skipped: %llu\n", s.users_evaluated,
-                (unsigned long long)n_held, (unsigned long long)s.edges_skipped);
-    std::printf("precision@N %g recall@N %g ndcg@N %g map@N %g mrr %g auc %g mpr %g\n", s.precision, s.recall, s.ndcg,
-                s.map, s.mrr, s.auc, s.mpr);
-    if (s.n_nan_held) std::printf("warning: %llu held-out scores were NaN and have no rank\n", (unsigned long long)s.n_nan_held);
-
-    if (!output.empty()) {
-        cfio::ShardWriter w(".", output, nshards);
-        for (uint32_t u = 0; u < nu; ++u) {
-            const uint32_t uid = uids.ids[u];
-            for (uint64_t e = hoff[u]; e < hoff[u + 1]; ++e) {
-                std::string& out = w.shard(uid);
-                cfio::append_u(out, uid);
-                out += '\t';
-                cfio::append_u(out, mids.ids[hitem[e]]);
-                out += '\t';
-                if (rank[e] == 0xffffffffu) out += "-1";
-                else cfio::append_u(out, rank[e]);
-                out += '\t';
-                cfio::append_u(out, users[u].n_cand);
-                out += '\n';
-            }
-        }
-        w.flush();
-    }
+    cfrank::print_rank_summary(s, h.n);
+    if (!output.empty()) cfrank::write_ranks(output, nshards, uids, mids, h, rank, users);
     cf_destroy(ctx);
     return 0;
 }

@@ -23,6 +23,7 @@
 #include "cf_factor_io.hpp"
 #include "cf_knn_cli.hpp"
 #include "cf_mf_cli.hpp"
+#include "cf_rank_cli.hpp"
 
 int main(int argc, char** argv) {
     const std::string factors = cfcli::opt(argc, argv, "factors", "");
@@ -89,24 +90,7 @@ int main(int argc, char** argv) {
     }
 
     std::vector<uint32_t> sel;
-    if (!users_file.empty()) {
-        const std::string text = cfio::read_file(users_file);
-        const char* p = text.data();
-        const char* e = p + text.size();
-        while (p < e) {
-            if (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') {
-                ++p;
-                continue;
-            }
-            uint32_t id = 0;
-            const auto r = std::from_chars(p, e, id);
-            if (r.ec != std::errc()) cfcli::die("--users: " + users_file + " holds something that is not a user id");
-            p = r.ptr;
-            const auto u = uids.at.find(id);
-            if (u == uids.at.end()) cfcli::die("user " + std::to_string(id) + " of " + users_file + " has no line in " + ufile);
-            sel.push_back(u->second);
-        }
-    }
+    if (!users_file.empty()) sel = cfrank::read_users(users_file, uids, ufile);
     const bool selected = !users_file.empty();
     const uint32_t n_out = selected ? (uint32_t)sel.size() : nu;
     if (selected && sel.empty()) sel.push_back(0);
@@ -131,24 +115,8 @@ int main(int argc, char** argv) {
                                 selected ? sel.data() : nullptr, N, items.data(), scores.data(), count.data(), &st),
                      "cf_mf_topn");
     }
-    std::printf("User blocks: %u  scoring kernels: %.3f ms  exclusion and selection kernels: %.3f ms\n", st.blocks,
-                st.score_ms, st.select_ms);
-    if (st.n_nan) std::printf("warning: %llu scores were NaN and are not listed\n", (unsigned long long)st.n_nan);
-
-    cfio::ShardWriter w(".", output, nshards);
-    for (uint32_t j = 0; j < n_out; ++j) {
-        const uint32_t uid = uids.ids[selected ? sel[j] : j];
-        std::string& out = w.shard(uid);
-        for (uint32_t r = 0; r < count[j]; ++r) {
-            cfio::append_u(out, uid);
-            out += '\t';
-            cfio::append_u(out, mids.ids[items[(size_t)j * N + r]]);
-            out += '\t';
-            cfio::append_g(out, scores[(size_t)j * N + r]);
-            out += '\n';
-        }
-    }
-    w.flush();
+    cfrank::print_topn_stats(st);
+    cfrank::write_lists(output, nshards, uids, mids, selected, sel, n_out, N, items, scores, count);
     cf_destroy(ctx);
     return 0;
 }

@@ -44,6 +44,7 @@
  *                                  MRR / AUC / expected percentile rank from the fitted factors
  *   cf_knn_topn                    : none: knn3 scores listed pairs only
  *   cf_knn_rank_eval               : none: knn3 scores listed pairs only
+ *   cf_ease_fit / _topn / _rank_eval : none: the closed-form item-item model (EASE)
  */
 #ifndef CF_ABI_H
 #define CF_ABI_H
@@ -1073,6 +1074,65 @@ int cf_bpr_sample(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_
 int cf_bpr_timing(cf_ctx* ctx, float ms[6]);
 /* CF_BPR_TRIES as compiled (test helper, needs no GPU). */
 int cf_debug_bpr_tries(void);
+
+/* ---- EASE (Steck, "Embarrassingly Shallow Autoencoders for Sparse Data", WWW 2019): the closed-form
+ * linear item-item model, as a fit and as a third score source of cf_mf_topn / cf_mf_rank_eval.  No
+ * reference counterpart ----
+ * Inputs of the fit: the TRAIN edges as a CSR by user (user_off / user_item / user_obs) whose item
+ * lists are STRICTLY ASCENDING, lambda > 0 and `binary`: the value of an edge is x = 1 when binary is
+ * nonzero, else (double) obs.
+ *   G = X^T X + lambda I   G[i][j] = sum over the users in ascending order, from a zero accumulator,
+ *                          of x_ui x_uj in fp64 (the product of two floats is exact in a double);
+ *                          lambda is added to the diagonal last.  G is symmetric bit for bit.
+ *   P = G^-1               in place, by unpivoted block Gauss-Jordan of block width
+ *                          cf_debug_ease_block() (every pivot block is a Schur complement of an SPD
+ *                          matrix).  The block width is a constant: the bytes of P depend on G only.
+ *   B[i][j] = -P[i][j] / P[j][j] for i != j, B[j][j] = 0
+ * B is n_items x n_items fp64 row-major and stays resident in the context until the next cf_ease_fit,
+ * cf_ease_upload or cf_destroy (cf_release_workspaces leaves it alone).  It is independent of the
+ * resident item graph: both can be resident at once.  An item without an edge has G row and column
+ * lambda e_j, so its row and column of B are zero; there is no special case.
+ * Score of item j for a profile (i_0, x_0), (i_1, x_1), .. (x_t = 1 when binary, else (double) rating):
+ *   s(u, j) = sum_t x_t B[i_t][j]   over the profile in the order given, from zero; each product is
+ *                                   rounded to double, then added (no fused multiply-add)
+ * The profile at scoring time is an argument, as cf_knn_topn's is; it need not be the fit's, and its
+ * items need not ascend.  Everything after the score is cf_mf_topn's / cf_mf_rank_eval's contract,
+ * unchanged (see cf_knn_topn).  There is no floating-point atomic and every reduction has a fixed
+ * order: B and every list are the same bytes across repeats, user-block sizes and selections.
+ *   cf_ease_fit      fits and keeps B.  n_items == 0 succeeds and leaves no B resident.
+ *   cf_ease_gram     the Gram stage alone, the kernel the fit runs: G [n_items^2] to the host
+ *   cf_ease_weights  *n_items = the resident B's size; B == NULL: the size only
+ *   cf_ease_upload   any B: signed, NaN allowed
+ *   cf_ease_timing   device times of the last fit: {Gram (with the by-item CSR), inversion, normalise}
+ * CF_EINVAL: lambda not finite or <= 0; null arrays; an offset array that does not start at 0 or
+ * decreases; an item >= n_items; a fit list that is not strictly ascending; cf_ease_upload with
+ * n_items == 0; plus every error of the mf calls.  CF_ESTATE: cf_ease_topn / cf_ease_rank_eval /
+ * cf_ease_weights with no B resident.  CF_ERANGE: n_items > 2^24, 2^32 or more edges, N >
+ * CF_TOPN_MAX_N.  CF_ENOMEM: B does not fit.  Empty calls succeed as the mf calls do. */
+int cf_ease_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t* user_off, const uint32_t* user_item,
+                const float* user_obs, int binary, double lambda);
+int cf_ease_gram(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t* user_off, const uint32_t* user_item,
+                 const float* user_obs, int binary, double lambda, double* G);
+int cf_ease_weights(cf_ctx* ctx, uint32_t* n_items, double* B);
+int cf_ease_upload(cf_ctx* ctx, uint32_t n_items, const double* B);
+int cf_ease_topn(cf_ctx* ctx, uint32_t n_users, const uint64_t* prof_off, const uint32_t* prof_item,
+                 const float* prof_rating, int binary, const uint64_t* excl_off, const uint32_t* excl_item,
+                 uint32_t n_sel, const uint32_t* sel_user, uint32_t N, uint32_t* items, double* scores,
+                 uint32_t* count, cf_topn_stats* stats);
+int cf_ease_rank_eval(cf_ctx* ctx, uint32_t n_users, const uint64_t* prof_off, const uint32_t* prof_item,
+                      const float* prof_rating, int binary, const uint64_t* excl_off, const uint32_t* excl_item,
+                      const uint64_t* held_off, const uint32_t* held_item, const double* held_w, uint32_t N,
+                      uint32_t* rank, cf_rank_user* users, cf_rank_summary* summary);
+int cf_ease_timing(cf_ctx* ctx, float ms[3]);
+/* P = G^-1 of the same inputs to the host, the fit without its last stage; the resident B is left as
+ * it is.  Test helper. */
+int cf_debug_ease_inverse(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t* user_off,
+                          const uint32_t* user_item, const float* user_obs, int binary, double lambda, double* P);
+/* The inversion's block width, the items per workgroup of the score kernel and the profile entries
+ * in flight per lane there: constants of cf_ease.hip; test helpers, need no GPU. */
+int cf_debug_ease_block(void);
+int cf_debug_ease_cols(void);
+int cf_debug_ease_unroll(void);
 
 #ifdef __cplusplus
 }
