@@ -309,6 +309,20 @@ def _rank_result(su, perm, rank, users, st):
     return RankEvalResult(out_rank, out_cand, users, summary, st)
 
 
+def _mf_source(U, V, bias_user, bias_item, mean):
+    """(n_users, the arguments of cf_mf_topn / cf_mf_rank_eval between n_users and the exclusions)."""
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    V = np.ascontiguousarray(V, dtype=np.float64)
+    if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
+        raise ValueError("U and V must be n_users x D and n_items x D")
+    n_users, n_items, D = U.shape[0], V.shape[0], U.shape[1]
+    bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
+    bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
+    if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
+        raise ValueError("bias_user / bias_item do not hold one value per user / item")
+    return n_users, (n_items, D, U, V, bu, bi, float(mean))
+
+
 _KNN_SCORE_MODES = {"sum": 0, "mean": 1}   # CF_KNN_SCORE_SUM / CF_KNN_SCORE_MEAN
 
 def _mf_factors(mats, ns, names, shapes):
@@ -1159,28 +1173,8 @@ class Context:
         U_u . V_i + (bias_item[i] + (mean + bias_user[u])), absent biases skipped, among the items
         that are not in the user's exclusion list.  exclude: (user, item) index arrays of the pairs
         to leave out (any order, repeats allowed).  A NaN score is never listed."""
-        U = np.ascontiguousarray(U, dtype=np.float64)
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
-            raise ValueError("U and V must be n_users x D and n_items x D")
-        n_users, n_items, D, N = U.shape[0], V.shape[0], U.shape[1], int(N)
-        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
-        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
-        if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
-            raise ValueError("bias_user / bias_item do not hold one value per user / item")
-        eoff, eitem = _exclusion_csr(exclude, n_users)
-        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
-        n_out = n_users if sel is None else len(sel)
-        if sel is not None and not len(sel):
-            sel = np.zeros(1, np.uint32)
-        items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
-        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
-        count = np.zeros(n_out, dtype=np.uint32)
-        st = _native.TopnStats()
-        self._chk(self.lib.cf_mf_topn(self.h, n_users, n_items, D, ptr(U), ptr(V), ptr(bu), ptr(bi), float(mean),
-                                      ptr(eoff), ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(items),
-                                      ptr(scores), ptr(count), byref(st)), "cf_mf_topn")
-        return TopnResult(items, scores, count, st)
+        n_users, head = _mf_source(U, V, bias_user, bias_item, mean)
+        return self._topn("cf_mf_topn", n_users, head, _exclusion_csr(exclude, n_users), users, N)
 
     def mf_rank_eval(self, U, V, N, held, *, exclude=None, bias_user=None, bias_item=None,
                      mean=0.0) -> "RankEvalResult":
@@ -1189,23 +1183,37 @@ class Context:
         cutoff N per user with their means and the expected percentile rank (cf_abi.h has the
         definitions).  held: (user, item[, weight]) arrays of the pairs to find, in any order; a
         repeated pair raises ValueError.  exclude: (user, item) arrays of the training pairs."""
-        U = np.ascontiguousarray(U, dtype=np.float64)
-        V = np.ascontiguousarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[1] != V.shape[1]:
-            raise ValueError("U and V must be n_users x D and n_items x D")
-        n_users, n_items, D, N = U.shape[0], V.shape[0], U.shape[1], int(N)
-        bu = None if bias_user is None else np.ascontiguousarray(bias_user, dtype=np.float64)
-        bi = None if bias_item is None else np.ascontiguousarray(bias_item, dtype=np.float64)
-        if (bu is not None and len(bu) != n_users) or (bi is not None and len(bi) != n_items):
-            raise ValueError("bias_user / bias_item do not hold one value per user / item")
-        eoff, eitem = _exclusion_csr(exclude, n_users)
+        n_users, head = _mf_source(U, V, bias_user, bias_item, mean)
+        return self._rank_eval("cf_mf_rank_eval", n_users, head, _exclusion_csr(exclude, n_users), held, N)
+
+    def _topn(self, name, n_users, head, excl, users, N) -> "TopnResult":
+        """The call of a cf_*_topn entry point: `head` = its arguments up to the exclusion CSR
+        `excl` (arrays, kept alive here), then the selection, N and the output buffers."""
+        N = int(N)
+        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
+        n_out = n_users if sel is None else len(sel)
+        if sel is not None and not len(sel):
+            sel = np.zeros(1, np.uint32)
+        items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
+        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
+        count = np.zeros(n_out, dtype=np.uint32)
+        st = _native.TopnStats()
+        args = [ptr(a) if isinstance(a, np.ndarray) else a for a in head]
+        self._chk(getattr(self.lib, name)(self.h, n_users, *args, ptr(excl[0]), ptr(excl[1]),
+                                          n_out if sel is not None else 0, ptr(sel), N, ptr(items), ptr(scores),
+                                          ptr(count), byref(st)), name)
+        return TopnResult(items, scores, count, st)
+
+    def _rank_eval(self, name, n_users, head, excl, held, N) -> "RankEvalResult":
+        """The call of a cf_*_rank_eval entry point: `head` and `excl` as in _topn, then the
+        held-out CSR of `held` (user, item, weight or None), N and the output buffers."""
         su, perm, hoff, hitem, hws = _held_csr(held, n_users)
         rank = np.zeros(max(len(su), 1), dtype=np.uint32)
         users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
         st = _native.RankSummary()
-        self._chk(self.lib.cf_mf_rank_eval(self.h, n_users, n_items, D, ptr(U), ptr(V), ptr(bu), ptr(bi), float(mean),
-                                           ptr(eoff), ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank),
-                                           ptr(users), byref(st)), "cf_mf_rank_eval")
+        args = [ptr(a) if isinstance(a, np.ndarray) else a for a in head]
+        self._chk(getattr(self.lib, name)(self.h, n_users, *args, ptr(excl[0]), ptr(excl[1]), ptr(hoff), ptr(hitem),
+                                          ptr(hws), int(N), ptr(rank), ptr(users), byref(st)), name)
         return _rank_result(su, perm, rank, users[:n_users], st)
 
     # -- top-N and ranking evaluation from the item graph (no reference counterpart) ----
@@ -1237,34 +1245,15 @@ class Context:
         w(m, i) > w_min, "mean" = that over the sum of those w (knn_predict's prediction, 0 without a
         neighbour).  exclude: "profile" (the user's own items), None, or (user, item) arrays."""
         n_users, off, it, rat, smode, eoff, eitem = self._knn_profile(user_off, items, ratings, mode, exclude)
-        N = int(N)
-        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
-        n_out = n_users if sel is None else len(sel)
-        if sel is not None and not len(sel):
-            sel = np.zeros(1, np.uint32)
-        out_items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
-        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
-        count = np.zeros(n_out, dtype=np.uint32)
-        st = _native.TopnStats()
-        self._chk(self.lib.cf_knn_topn(self.h, n_users, ptr(off), ptr(it), ptr(rat), smode, float(w_min), ptr(eoff),
-                                       ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(out_items),
-                                       ptr(scores), ptr(count), byref(st)), "cf_knn_topn")
-        return TopnResult(out_items, scores, count, st)
+        return self._topn("cf_knn_topn", n_users, (off, it, rat, smode, float(w_min)), (eoff, eitem), users, N)
 
     def knn_rank_eval(self, user_off, items, ratings, N, held, *, mode="sum", w_min=0.1, exclude="profile",
                       weights=None) -> "RankEvalResult":
         """cf_knn_rank_eval: mf_rank_eval with the scores of knn_topn.  held: (user, item) arrays of
         the pairs to find, in any order; weights: one per held pair (mpr only)."""
         n_users, off, it, rat, smode, eoff, eitem = self._knn_profile(user_off, items, ratings, mode, exclude)
-        N = int(N)
-        su, perm, hoff, hitem, hws = _held_csr((held[0], held[1], weights), n_users)
-        rank = np.zeros(max(len(su), 1), dtype=np.uint32)
-        users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
-        st = _native.RankSummary()
-        self._chk(self.lib.cf_knn_rank_eval(self.h, n_users, ptr(off), ptr(it), ptr(rat), smode, float(w_min), ptr(eoff),
-                                            ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank), ptr(users),
-                                            byref(st)), "cf_knn_rank_eval")
-        return _rank_result(su, perm, rank, users[:n_users], st)
+        return self._rank_eval("cf_knn_rank_eval", n_users, (off, it, rat, smode, float(w_min)), (eoff, eitem),
+                               (held[0], held[1], weights), N)
 
     # -- EASE: the closed-form item-item model (no reference counterpart) --------------
     @staticmethod
@@ -1340,34 +1329,15 @@ class Context:
         need not be the fit's: any user can be scored.  exclude: "profile" (the user's own items),
         None, or (user, item) arrays."""
         n_users, off, it, rat, eoff, eitem = self._ease_profile(user_off, items, ratings, exclude)
-        N = int(N)
-        sel = None if users is None else np.ascontiguousarray(users, dtype=np.uint32)
-        n_out = n_users if sel is None else len(sel)
-        if sel is not None and not len(sel):
-            sel = np.zeros(1, np.uint32)
-        out_items = np.full((n_out, max(N, 0)), 0xFFFFFFFF, dtype=np.uint32)
-        scores = np.zeros((n_out, max(N, 0)), dtype=np.float64)
-        count = np.zeros(n_out, dtype=np.uint32)
-        st = _native.TopnStats()
-        self._chk(self.lib.cf_ease_topn(self.h, n_users, ptr(off), ptr(it), ptr(rat), int(bool(binary)), ptr(eoff),
-                                        ptr(eitem), n_out if sel is not None else 0, ptr(sel), N, ptr(out_items),
-                                        ptr(scores), ptr(count), byref(st)), "cf_ease_topn")
-        return TopnResult(out_items, scores, count, st)
+        return self._topn("cf_ease_topn", n_users, (off, it, rat, int(bool(binary))), (eoff, eitem), users, N)
 
     def ease_rank_eval(self, user_off, items, ratings, N, held, *, binary=False, exclude="profile",
                        weights=None) -> "RankEvalResult":
         """cf_ease_rank_eval: mf_rank_eval with the scores of ease_topn.  held: (user, item) arrays of
         the pairs to find, in any order; weights: one per held pair (mpr only)."""
         n_users, off, it, rat, eoff, eitem = self._ease_profile(user_off, items, ratings, exclude)
-        N = int(N)
-        su, perm, hoff, hitem, hws = _held_csr((held[0], held[1], weights), n_users)
-        rank = np.zeros(max(len(su), 1), dtype=np.uint32)
-        users = np.zeros(max(n_users, 1), dtype=RANK_USER_DTYPE)
-        st = _native.RankSummary()
-        self._chk(self.lib.cf_ease_rank_eval(self.h, n_users, ptr(off), ptr(it), ptr(rat), int(bool(binary)), ptr(eoff),
-                                             ptr(eitem), ptr(hoff), ptr(hitem), ptr(hws), N, ptr(rank), ptr(users),
-                                             byref(st)), "cf_ease_rank_eval")
-        return _rank_result(su, perm, rank, users[:n_users], st)
+        return self._rank_eval("cf_ease_rank_eval", n_users, (off, it, rat, int(bool(binary))), (eoff, eitem),
+                               (held[0], held[1], weights), N)
 
     # -- truncated SVD by restarted Lanczos (svd.cpp:304-505) ------------------------
     @staticmethod

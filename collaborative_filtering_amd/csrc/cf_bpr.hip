@@ -13,8 +13,8 @@
 //      factors, neg[p] and g[p] = 1 / (1 + exp(x)) are written, and softplus(-x) goes into the
 //      block's partial (group g takes edges g, g + 32, .. in order, then a tree; the partials are
 //      added by als_error_final_kernel).
-//   2. The negative lists: a stable sort of (neg[p], p) (cf_sort.h) and a lower-bound pass give a
-//      CSR of the triples by negative item, p ascending within an item; skipped edges carry
+//   2. The negative lists: lists_by_key (cf_sort.h: a stable sort of (neg[p], p), then a lower-bound
+//      pass) gives a CSR of the triples by negative item, p ascending within an item; skipped edges carry
 //      UINT32_MAX and sort past the end.  Its class lists are compacted anew every sweep.
 //   3. Three policies of the vertex reduction of cf_mf_reduce.h (its degree classes, LDS partials
 //      and HBM segment workspace unchanged):
@@ -161,26 +161,6 @@ __global__ __launch_bounds__(kAT) void bpr_sample_kernel(BprDev f, uint64_t key_
         for (int w = 0; w < kWaves; ++w) t += s_c[w][threadIdx.x];
         if (t) atomicAdd(&counters[threadIdx.x], (unsigned long long)t);
     }
-}
-
-// noff[i] = the first position of the sorted negatives that is >= i, i = 0 .. n_items (skipped
-// edges carry kSkipped > every item and lie past noff[n_items]).
-__global__ __launch_bounds__(kAT) void bpr_offsets_kernel(const uint32_t* __restrict__ key, uint64_t n, uint32_t n_items,
-                                                         uint64_t* noff) {
-    const uint64_t i = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (i > n_items) return;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if ((uint64_t)key[mid] < i) lo = mid + 1;
-        else hi = mid;
-    }
-    noff[i] = lo;
-}
-
-__global__ __launch_bounds__(kAT) void bpr_iota_kernel(uint32_t* out, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (i < n) out[i] = (uint32_t)i;
 }
 
 __global__ __launch_bounds__(kAT) void bpr_commit_kernel(double* __restrict__ dst, const double* __restrict__ src,
@@ -400,26 +380,15 @@ void carve_bpr(Carver& c, BprLayout& L, uint32_t nu, uint32_t ni, uint64_t nnz, 
     L.counters = c.take<unsigned long long>(2);
 }
 
-// The user CSR of both entry points: offsets, index range, strictly ascending lists.
+// The user CSR of both entry points (check_csr's two halves) with BPR's own limits between them.
 int check_user_lists(cf_ctx* ctx, const char* fn, uint32_t n_users, uint32_t n_items, const uint64_t* user_off,
                      const uint32_t* user_item, uint64_t* nnz_out) {
     const std::string f(fn);
-    if (n_users && !user_off) return cf_set_error(ctx, CF_EINVAL, f + ": null argument");
+    if (n_users) CF_TRY(check_csr_shape(ctx, fn, "user", n_users, user_off, user_item));
     const uint64_t nnz = n_users ? user_off[n_users] : 0;
-    if (n_users) {
-        if (user_off[0] != 0) return cf_set_error(ctx, CF_EINVAL, f + ": user offsets do not start at 0");
-        for (uint32_t v = 0; v < n_users; ++v)
-            if (user_off[v + 1] < user_off[v]) return cf_set_error(ctx, CF_EINVAL, f + ": user offsets decrease");
-    }
-    if (nnz && !user_item) return cf_set_error(ctx, CF_EINVAL, f + ": null edge array");
     if (n_items == kSkipped) return cf_set_error(ctx, CF_ERANGE, f + ": 2^32 - 1 items");
     if (nnz >= (1ull << 31)) return cf_set_error(ctx, CF_ERANGE, f + ": 2^31 or more edges");
-    for (uint32_t v = 0; v < n_users; ++v)
-        for (uint64_t e = user_off[v]; e < user_off[v + 1]; ++e) {
-            if (user_item[e] >= n_items) return cf_set_error(ctx, CF_EINVAL, f + ": user index out of range");
-            if (e > user_off[v] && user_item[e] <= user_item[e - 1])
-                return cf_set_error(ctx, CF_EINVAL, f + ": a user's items are not strictly ascending");
-        }
+    if (n_users) CF_TRY(check_csr_index(ctx, fn, "user", n_users, user_off, user_item, n_items, true));
     *nnz_out = nnz;
     return CF_OK;
 }
@@ -553,8 +522,7 @@ extern "C" int cf_bpr_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         return cf_set_error(ctx, CF_ERANGE, "cf_bpr_fit: too many segments");
     hipStream_t st = nullptr;
     size_t sort_bytes = 0;
-    CF_HIP_CHECK(ctx, sort_pairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                                 (uint32_t*)nullptr, nnz, 32, st));
+    CF_HIP_CHECK(ctx, lists_by_key(nullptr, sort_bytes, nullptr, nullptr, nullptr, false, nullptr, nnz, n_items, nullptr, 32, st));
     const bool bias = bias_item != nullptr;
     BprLayout L{};
     CF_TRY(carve_workspace(ctx, [&](Carver& c) { carve_bpr(c, L, n_users, n_items, nnz, (int)D, bias, segs, sort_bytes); }));
@@ -572,7 +540,7 @@ extern "C" int cf_bpr_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
     CF_TRY(upload(ctx, (const double*)f.V, (const double*)V, (size_t)n_items * D));
     if (bias) CF_TRY(upload(ctx, (const double*)f.b, (const double*)bias_item, n_items));
     for (int k = 0; k < 3; ++k) CF_HIP_CHECK(ctx, hipMemset(L.side[k].active, 0, L.side[k].n));
-    hipLaunchKernelGGL(bpr_iota_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, L.iota, nnz);
+    hipLaunchKernelGGL(iota_kernel<uint32_t>, dim3(blocks_for(nnz)), dim3(kAT), 0, st, L.iota, nnz);   // once for every sweep
 
     // the users and the items by their positives: classed once per fit
     uint32_t rec[3][4];
@@ -601,10 +569,8 @@ extern "C" int cf_bpr_fit(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, uint3
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
         // 2. the negative CSR and its class lists
         size_t tb = sort_bytes;
-        CF_HIP_CHECK(ctx, sort_pairs(L.sort_tmp, tb, (const uint32_t*)f.neg, L.nkey, (const uint32_t*)L.iota, f.npos, nnz, 32,
-                                     st));
-        hipLaunchKernelGGL(bpr_offsets_kernel, dim3(blocks_for((uint64_t)n_items + 1)), dim3(kAT), 0, st,
-                           (const uint32_t*)L.nkey, nnz, n_items, f.noff);
+        // all 32 bits: skipped edges carry kSkipped and sort past noff[n_items]
+        CF_HIP_CHECK(ctx, lists_by_key(L.sort_tmp, tb, f.neg, L.nkey, L.iota, false, f.npos, nnz, n_items, f.noff, 32, st));
         launch_classes(L.side[2], L.lists[2], st);
         CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
         CF_HIP_CHECK(ctx, hipGetLastError());

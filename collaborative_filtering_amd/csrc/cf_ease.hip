@@ -4,7 +4,7 @@
 // (cf_ease_topn, cf_ease_rank_eval): s(u, j) = sum_t x_t B[i_t][j] over the profile.  DESIGN 3.22.
 //
 //   ease_gram_kernel    one workgroup per row i of G: item i's users in ascending order (the by-item
-//                       CSR: a stable sort of the edge positions by item and a lower bound per item),
+//                       CSR: lists_by_key of cf_sort.h over the edge positions, once per fit),
 //                       and per user u the lanes stride over u's list, G[i][j] += x_ui x_uj as a plain
 //                       read-modify-write (the j of one strictly ascending list differ: no two lanes
 //                       collide); __syncthreads() between users orders two users' accesses to one j.
@@ -43,27 +43,6 @@ constexpr uint32_t kEaseMaxItems = 1u << 24;
 constexpr unsigned kGridY = 65535;
 
 static_assert(kEaseB == kTU && kEaseB == kTI && kEaseB == 2 * kKC, "a block step is one 64 x 64 tile, two staged passes deep");
-
-// ---- by-item CSR -----------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(kAT) void ease_iota_kernel(uint32_t* out, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (i < n) out[i] = (uint32_t)i;
-}
-
-// ioff[i] = the first position of the sorted keys that holds an item >= i (i = 0 .. n_items).
-__global__ __launch_bounds__(kAT) void ease_offsets_kernel(const uint32_t* __restrict__ key, uint64_t n, uint32_t n_items,
-                                                          uint64_t* __restrict__ ioff) {
-    const uint64_t i = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-    if (i > n_items) return;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (key[mid] < i) lo = mid + 1;
-        else hi = mid;
-    }
-    ioff[i] = lo;
-}
 
 // ---- Gram ------------------------------------------------------------------------------------------
 
@@ -288,26 +267,6 @@ __global__ __launch_bounds__(kAT) void ease_score_kernel(const double* __restric
 
 // ---- host ------------------------------------------------------------------------------------------
 
-// A CSR of n lists over items below n_items: offsets from 0 that do not decrease, items in range
-// and, for the fit, strictly ascending per list.
-int ease_check_csr(cf_ctx* ctx, const std::string& fn, const char* what, uint32_t n, uint32_t n_items,
-                   const uint64_t* off, const uint32_t* item, const float* val, bool ascending) {
-    if (!off) return cf_set_error(ctx, CF_EINVAL, fn + ": null " + what + " offsets");
-    if (off[0] != 0) return cf_set_error(ctx, CF_EINVAL, fn + ": " + what + " offsets do not start at 0");
-    for (uint32_t u = 0; u < n; ++u)
-        if (off[u + 1] < off[u]) return cf_set_error(ctx, CF_EINVAL, fn + ": " + what + " offsets decrease");
-    const uint64_t nnz = off[n];
-    if (nnz && (!item || !val)) return cf_set_error(ctx, CF_EINVAL, fn + ": null " + what + " array");
-    for (uint64_t e = 0; e < nnz; ++e)
-        if (item[e] >= n_items) return cf_set_error(ctx, CF_EINVAL, fn + ": " + what + " item out of range");
-    if (ascending)
-        for (uint32_t u = 0; u < n; ++u)
-            for (uint64_t e = off[u] + 1; e < off[u + 1]; ++e)
-                if (item[e] <= item[e - 1])
-                    return cf_set_error(ctx, CF_EINVAL, fn + ": the items of a " + what + " list are not strictly ascending");
-    return CF_OK;
-}
-
 struct EaseFitLayout {
     uint64_t* uoff;
     uint32_t* uitem;
@@ -335,8 +294,8 @@ int ease_stages(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t*
     size_t sort_bytes = 0;
     const int bits = bits_for(n_items);
     if (nnz)
-        CF_HIP_CHECK(ctx, sort_pairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                     (const uint32_t*)nullptr, (uint32_t*)nullptr, nnz, bits, st));
+        CF_HIP_CHECK(ctx, lists_by_key(nullptr, sort_bytes, nullptr, nullptr, nullptr, true, nullptr, nnz, n_items, nullptr,
+                                       bits, st));
     EaseFitLayout L{};
     CF_TRY(carve_workspace(ctx, [&](Carver& c) {
         L.uoff = c.take<uint64_t>((size_t)n_users + 1);
@@ -363,13 +322,9 @@ int ease_stages(cf_ctx* ctx, uint32_t n_users, uint32_t n_items, const uint64_t*
 
     CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
     if (nnz) {
-        hipLaunchKernelGGL(ease_iota_kernel, dim3(blocks_for(nnz)), dim3(kAT), 0, st, L.iota, nnz);
         size_t tb = sort_bytes;
         // stable: the positions of one item stay ascending, and with them its users
-        CF_HIP_CHECK(ctx, sort_pairs(L.sort_tmp, tb, (const uint32_t*)L.uitem, L.key, (const uint32_t*)L.iota, L.ipos, nnz,
-                                     bits, st));
-        hipLaunchKernelGGL(ease_offsets_kernel, dim3(blocks_for((uint64_t)n_items + 1)), dim3(kAT), 0, st,
-                           (const uint32_t*)L.key, nnz, n_items, L.ioff);
+        CF_HIP_CHECK(ctx, lists_by_key(L.sort_tmp, tb, L.uitem, L.key, L.iota, true, L.ipos, nnz, n_items, L.ioff, bits, st));
     } else {
         CF_HIP_CHECK(ctx, hipMemsetAsync(L.ioff, 0, sizeof(uint64_t) * ((size_t)n_items + 1), st));
     }
@@ -416,7 +371,7 @@ int ease_check_fit(cf_ctx* ctx, const std::string& fn, uint32_t n_users, uint32_
     if (!std::isfinite(lambda) || !(lambda > 0.0)) return cf_set_error(ctx, CF_EINVAL, fn + ": lambda is not finite and > 0");
     if (n_items > kEaseMaxItems) return cf_set_error(ctx, CF_ERANGE, fn + ": more than 2^24 items");
     if (n_users) {
-        CF_TRY(ease_check_csr(ctx, fn, "user", n_users, n_items, user_off, user_item, user_obs, true));
+        CF_TRY(check_csr(ctx, fn.c_str(), "user", n_users, user_off, user_item, n_items, true, true, user_obs));
         if (user_off[n_users] >> 32) return cf_set_error(ctx, CF_ERANGE, fn + ": 2^32 or more edges");
     }
     return CF_OK;
@@ -443,47 +398,15 @@ int ease_to_host(cf_ctx* ctx, const char* name, uint32_t n_users, uint32_t n_ite
 
 // The B source of the panel drivers: the profiles in the workspace, B in the context,
 // ease_score_kernel over the block's rows and column tiles.
-struct EasePanelSource final : PanelSource {
-    uint32_t n_users = 0, n_items = 0;
-    const uint64_t* prof_off = nullptr;
-    const uint32_t* prof_item = nullptr;
-    const float* prof_rating = nullptr;
+struct EasePanelSource final : ProfilePanelSource {
     int binary = 0;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_item = nullptr;
-    float* d_rating = nullptr;
 
-    void carve(Carver& c) {
-        const uint64_t nnz = prof_off[n_users];
-        d_off = c.take<uint64_t>((size_t)n_users + 1);
-        d_item = c.take<uint32_t>(nnz);
-        d_rating = c.take<float>(nnz);
-    }
-    bool valid() const override { return true; }   // ease_check has seen the profile arrays
-    size_t workspace(uint32_t) const override {
-        EasePanelSource s = *this;
-        Carver c;
-        s.carve(c);
-        return c.pos;
-    }
-    int upload(cf_ctx* ctx, void* ws, uint32_t, hipStream_t, float*) override {
-        Carver c;
-        c.base = static_cast<char*>(ws);
-        carve(c);
-        const uint64_t nnz = prof_off[n_users];
-        CF_HIP_CHECK(ctx, hipMemcpy(d_off, prof_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
-        if (nnz) {
-            CF_HIP_CHECK(ctx, hipMemcpy(d_item, prof_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-            CF_HIP_CHECK(ctx, hipMemcpy(d_rating, prof_rating, sizeof(float) * nnz, hipMemcpyHostToDevice));
-        }
-        return CF_OK;
-    }
     int fill(cf_ctx* ctx, hipStream_t st, const uint32_t* d_sel, uint32_t b0, uint32_t nb, uint64_t* d_panel) override {
         const uint64_t tiles = ((uint64_t)n_items + kEaseCols - 1) / kEaseCols;
         if (tiles * nb > 0x7fffffffull)
             return cf_set_error(ctx, CF_ERANGE, "EASE score: users per block x items exceed the launch grid");
         hipLaunchKernelGGL(ease_score_kernel, dim3((unsigned)(tiles * nb)), dim3(kAT), 0, st, (const double*)ctx->d_ease_B,
-                           n_items, (const uint64_t*)d_off, (const uint32_t*)d_item, (const float*)d_rating, binary, d_sel,
+                           n_items, (const uint64_t*)dev.off, (const uint32_t*)dev.item, (const float*)dev.rating, binary, d_sel,
                            b0, nb, d_panel);
         return CF_OK;
     }
@@ -493,7 +416,7 @@ struct EasePanelSource final : PanelSource {
 int ease_check(cf_ctx* ctx, const std::string& fn, uint32_t n_users, const uint64_t* prof_off, const uint32_t* prof_item,
                const float* prof_rating, int binary, EasePanelSource* src) {
     if (!ctx->d_ease_B) return cf_set_error(ctx, CF_ESTATE, fn + ": no EASE weights resident");
-    CF_TRY(ease_check_csr(ctx, fn, "profile", n_users, ctx->ease_n, prof_off, prof_item, prof_rating, false));
+    CF_TRY(check_csr(ctx, fn.c_str(), "profile", n_users, prof_off, prof_item, ctx->ease_n, false, true, prof_rating));
     src->n_users = n_users, src->n_items = ctx->ease_n;
     src->prof_off = prof_off, src->prof_item = prof_item, src->prof_rating = prof_rating;
     src->binary = binary ? 1 : 0;

@@ -187,50 +187,33 @@ size_t knn_lds_pad(cf_ctx* ctx) {
     return std::min(kMaxDynamic, (kLds / w) & ~(size_t)1023);
 }
 
-// The graph source of the panel drivers: the profiles in the workspace (and the sw plane of MEAN
-// mode), the in-lists in the context, knn_score_kernel over the block's rows.
-struct KnnPanelSource final : PanelSource {
-    uint32_t n_users = 0, n_items = 0;
-    const uint64_t* prof_off = nullptr;
-    const uint32_t* prof_item = nullptr;
-    const float* prof_rating = nullptr;
+// The graph source of the panel drivers: after the profiles, the sw plane of MEAN mode in the
+// workspace; the in-lists in the context, knn_score_kernel over the block's rows.
+struct KnnPanelSource final : ProfilePanelSource {
     int mode = CF_KNN_SCORE_SUM;
     double w_min = 0.0;
-    uint64_t* d_off = nullptr;
-    uint32_t* d_item = nullptr;
-    float* d_rating = nullptr;
     uint64_t* d_plane = nullptr;
 
-    void carve(Carver& c, uint32_t ub) {
-        const uint64_t nnz = prof_off[n_users];
-        d_off = c.take<uint64_t>((size_t)n_users + 1);
-        d_item = c.take<uint32_t>(nnz);
-        d_rating = c.take<float>(nnz);
-        d_plane = mode == CF_KNN_SCORE_MEAN ? c.take<uint64_t>((size_t)ub * n_items) : nullptr;
+    uint64_t* carve_plane(Carver& c, uint32_t ub) const {
+        return mode == CF_KNN_SCORE_MEAN ? c.take<uint64_t>((size_t)ub * n_items) : nullptr;
     }
-    bool valid() const override { return true; }   // cf_knn_check has seen the profile arrays
     size_t workspace(uint32_t ub) const override {
-        KnnPanelSource s = *this;
         Carver c;
-        s.carve(c, ub);
+        carve(c);
+        carve_plane(c, ub);
         return c.pos;
     }
     int upload(cf_ctx* ctx, void* ws, uint32_t ub, hipStream_t st, float* score_ms) override {
         Carver c;
         c.base = static_cast<char*>(ws);
-        carve(c, ub);
-        const uint64_t nnz = prof_off[n_users];
-        CF_HIP_CHECK(ctx, hipMemcpy(d_off, prof_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
-        if (nnz) {
-            CF_HIP_CHECK(ctx, hipMemcpy(d_item, prof_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-            CF_HIP_CHECK(ctx, hipMemcpy(d_rating, prof_rating, sizeof(float) * nnz, hipMemcpyHostToDevice));
-        }
+        CF_TRY(upload_profiles(ctx, c));
+        d_plane = carve_plane(c, ub);
         return knn_in_lists(ctx, w_min, st, score_ms);
     }
     int fill(cf_ctx* ctx, hipStream_t st, const uint32_t* d_sel, uint32_t b0, uint32_t nb, uint64_t* d_panel) override {
         hipLaunchKernelGGL(knn_score_kernel, dim3(nb), dim3(kAT), knn_lds_pad(ctx), st, (const uint64_t*)ctx->d_knn_in_off,
-                           (const uint32_t*)ctx->d_knn_in_m, (const float*)ctx->d_knn_in_w, (const uint64_t*)d_off,
-                           (const uint32_t*)d_item, (const float*)d_rating, d_sel, b0, n_items,
+                           (const uint32_t*)ctx->d_knn_in_m, (const float*)ctx->d_knn_in_w, (const uint64_t*)dev.off,
+                           (const uint32_t*)dev.item, (const float*)dev.rating, d_sel, b0, n_items,
                            mode == CF_KNN_SCORE_MEAN ? 1 : 0, d_panel, d_plane);
         return CF_OK;
     }
@@ -244,14 +227,7 @@ int cf_knn_check(cf_ctx* ctx, const std::string& fn, uint32_t n_users, const uin
     if (score_mode != CF_KNN_SCORE_SUM && score_mode != CF_KNN_SCORE_MEAN)
         return cf_set_error(ctx, CF_EINVAL, fn + ": unknown score mode");
     if (!std::isfinite(w_min) || w_min < 0.0) return cf_set_error(ctx, CF_EINVAL, fn + ": w_min is not finite and >= 0");
-    if (!prof_off) return cf_set_error(ctx, CF_EINVAL, fn + ": null profile offsets");
-    if (prof_off[0] != 0) return cf_set_error(ctx, CF_EINVAL, fn + ": profile offsets do not start at 0");
-    for (uint32_t u = 0; u < n_users; ++u)
-        if (prof_off[u + 1] < prof_off[u]) return cf_set_error(ctx, CF_EINVAL, fn + ": profile offsets decrease");
-    const uint64_t nnz = prof_off[n_users];
-    if (nnz && (!prof_item || !prof_rating)) return cf_set_error(ctx, CF_EINVAL, fn + ": null profile array");
-    for (uint64_t e = 0; e < nnz; ++e)
-        if (prof_item[e] >= ctx->n_items) return cf_set_error(ctx, CF_EINVAL, fn + ": profile item out of range");
+    CF_TRY(check_csr(ctx, fn.c_str(), "profile", n_users, prof_off, prof_item, ctx->n_items, false, true, prof_rating));
     src->n_users = n_users, src->n_items = ctx->n_items;
     src->prof_off = prof_off, src->prof_item = prof_item, src->prof_rating = prof_rating;
     src->mode = score_mode, src->w_min = w_min;

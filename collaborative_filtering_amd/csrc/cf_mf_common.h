@@ -392,15 +392,41 @@ inline bool transpose_counts_agree(uint32_t n_a, const uint64_t* off_a, const ui
     return true;
 }
 
-inline int check_csr(cf_ctx* ctx, const char* fn, const char* what, uint32_t n, const uint64_t* off,
-                     const uint32_t* nbr, uint32_t n_other) {
+// The CSR check of every entry point, in two halves so that a caller's own limits can stand
+// between them (cf_bpr.hip).  The shape: offsets present, from 0 and not decreasing, and the edge
+// arrays present where there are edges (`val` counts only with has_val: a CSR without values
+// passes neither).
+inline int check_csr_shape(cf_ctx* ctx, const char* fn, const char* what, uint32_t n, const uint64_t* off,
+                           const uint32_t* nbr, bool has_val = false, const void* val = nullptr) {
     const std::string head = std::string(fn) + ": " + what;
+    if (!off) return cf_set_error(ctx, CF_EINVAL, head + " offsets are null");
     if (off[0] != 0) return cf_set_error(ctx, CF_EINVAL, head + " offsets do not start at 0");
     for (uint32_t v = 0; v < n; ++v)
         if (off[v + 1] < off[v]) return cf_set_error(ctx, CF_EINVAL, head + " offsets decrease");
+    if (off[n] && (!nbr || (has_val && !val))) return cf_set_error(ctx, CF_EINVAL, head + " edge array is null");
+    return CF_OK;
+}
+
+// The indices of a CSR of good shape: below n_other and, with `ascending`, strictly ascending in
+// every list.
+inline int check_csr_index(cf_ctx* ctx, const char* fn, const char* what, uint32_t n, const uint64_t* off,
+                           const uint32_t* nbr, uint32_t n_other, bool ascending = false) {
+    const std::string head = std::string(fn) + ": " + what;
     for (uint64_t e = 0; e < off[n]; ++e)
         if (nbr[e] >= n_other) return cf_set_error(ctx, CF_EINVAL, head + " index out of range");
+    if (ascending)
+        for (uint32_t v = 0; v < n; ++v)
+            for (uint64_t e = off[v] + 1; e < off[v + 1]; ++e)
+                if (nbr[e] <= nbr[e - 1])
+                    return cf_set_error(ctx, CF_EINVAL, head + " lists are not strictly ascending");
     return CF_OK;
+}
+
+inline int check_csr(cf_ctx* ctx, const char* fn, const char* what, uint32_t n, const uint64_t* off,
+                     const uint32_t* nbr, uint32_t n_other, bool ascending = false, bool has_val = false,
+                     const void* val = nullptr) {
+    CF_TRY(check_csr_shape(ctx, fn, what, n, off, nbr, has_val, val));
+    return check_csr_index(ctx, fn, what, n, off, nbr, n_other, ascending);
 }
 
 // The argument checks cf_als_fit and cf_sgd_fit share: D, the two CSRs and their consistency.

@@ -16,7 +16,9 @@
 // The device returns integers only and integer sums take any order, so the ranks do not depend on
 // the block size; the metrics are computed on the host from them in fixed orders (rank_metrics).
 // The only atomic is the integer count of NaN held-out items.
-// The host driver (cf_rank_drive) takes the panel's filler as a PanelSource, as cf_topn_drive does.
+// The host driver (cf_rank_drive: its checks, the evaluated users, the held-out arrays, the count
+// kernel, the copies back and the metrics) takes the panel's filler as a PanelSource and runs the
+// user blocks through PanelBlocks (cf_topn_panel.h), as cf_topn_drive does.
 
 #include <algorithm>
 #include <cmath>
@@ -115,20 +117,6 @@ __global__ __launch_bounds__(kAT) void rank_count_kernel(const uint64_t* __restr
     }
 }
 
-struct RankLayout {
-    void* src;   // the score source's part (PanelSource::workspace)
-    uint64_t* excl_off;
-    uint32_t* excl_item;
-    uint64_t* sel_off;
-    uint32_t* sel;
-    uint64_t* held_off;
-    uint32_t* held_item;
-    uint64_t* panel;
-    uint32_t* out_rank;
-    uint32_t* out_ncand;
-    unsigned long long* n_nan_held;
-};
-
 // The record of one user from its C candidates and the ranks of its held-out edges (CSR order,
 // kRankNone = skipped), and the user's share of the percentile-rank sums.  `sorted` is scratch.
 // Every sum runs in ascending rank order.
@@ -200,23 +188,11 @@ int cf_rank_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_us
                   const uint32_t* held_item, const double* held_w, uint32_t N, uint32_t* rank, cf_rank_user* users,
                   cf_rank_summary* summary) {
     const std::string fn = name;
-    if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
-    if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
-    if ((excl_off == nullptr) != (excl_item == nullptr))
-        return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
-    if (!held_off) return cf_set_error(ctx, CF_EINVAL, fn + ": null held-out CSR");
+    CF_TRY(panel_check_head(ctx, fn, N, excl_off, excl_item));
+    if (!held_off) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets are null");
     if (excl_off && n_users) CF_TRY(check_csr(ctx, name, "exclusion", n_users, excl_off, excl_item, n_items));
-    if (held_off[0] != 0) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets do not start at 0");
-    for (uint32_t u = 0; u < n_users; ++u)
-        if (held_off[u + 1] < held_off[u]) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out offsets decrease");
+    CF_TRY(check_csr(ctx, name, "held-out", n_users, held_off, held_item, n_items, true));
     const uint64_t n_held = held_off[n_users];
-    if (n_held && !held_item) return cf_set_error(ctx, CF_EINVAL, fn + ": null held-out CSR");
-    for (uint32_t u = 0; u < n_users; ++u)
-        for (uint64_t e = held_off[u]; e < held_off[u + 1]; ++e) {
-            if (held_item[e] >= n_items) return cf_set_error(ctx, CF_EINVAL, fn + ": held-out index out of range");
-            if (e > held_off[u] && held_item[e] <= held_item[e - 1])
-                return cf_set_error(ctx, CF_EINVAL, fn + ": held-out items of a user are not strictly ascending");
-        }
     if ((n_users && !users) || (n_held && !rank)) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
     if (summary) *summary = cf_rank_summary{};
     for (uint32_t u = 0; u < n_users; ++u) users[u] = cf_rank_user{};
@@ -231,83 +207,37 @@ int cf_rank_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_us
     const uint32_t n_eval = (uint32_t)sel.size();
     std::vector<uint64_t> hoff((size_t)n_eval + 1, 0);
     for (uint32_t j = 0; j < n_eval; ++j) hoff[j + 1] = held_off[sel[j] + 1];
-    const uint64_t nnz = excl_off ? excl_off[n_users] : 0;
-    std::vector<uint64_t> sel_off;   // the evaluated users' own prefix of exclusion counts
-    if (nnz) {
-        sel_off.assign((size_t)n_eval + 1, 0);
-        for (uint32_t j = 0; j < n_eval; ++j) sel_off[j + 1] = sel_off[j] + (excl_off[sel[j] + 1] - excl_off[sel[j]]);
-    }
-    const uint32_t ub = topn_block_users(ctx, n_items, n_eval);
-    const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
-    if ((uint64_t)((ub + kTU - 1) / kTU) * n_it > 0x7fffffffull)
-        return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
 
-    RankLayout L{};
-    const size_t src_bytes = src.workspace(ub);
-    for (int pass = 0; pass < 2; ++pass) {
-        Carver c;
-        if (pass) c.base = static_cast<char*>(ctx->d_als);
-        L.src = c.take<char>(src_bytes);
-        L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
-        L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
-        L.sel_off = nnz ? c.take<uint64_t>(sel_off.size()) : nullptr;
-        L.sel = c.take<uint32_t>(n_eval);
-        L.held_off = c.take<uint64_t>(hoff.size());
-        L.held_item = c.take<uint32_t>(n_held);
-        L.panel = c.take<uint64_t>((size_t)ub * n_items);
-        L.out_rank = c.take<uint32_t>(n_held);
-        L.out_ncand = c.take<uint32_t>(ub);
-        L.n_nan_held = c.take<unsigned long long>(1);
-        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
-    }
-    hipStream_t st = nullptr;
-    float score_ms = 0.0f, rank_ms = 0.0f;
-    CF_TRY(src.upload(ctx, L.src, ub, st, &score_ms));
-    if (nnz) {
-        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(L.sel_off, sel_off.data(), sizeof(uint64_t) * sel_off.size(), hipMemcpyHostToDevice));
-    }
-    CF_HIP_CHECK(ctx, hipMemcpy(L.sel, sel.data(), sizeof(uint32_t) * n_eval, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(L.held_off, hoff.data(), sizeof(uint64_t) * hoff.size(), hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemcpy(L.held_item, held_item, sizeof(uint32_t) * n_held, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemset(L.n_nan_held, 0, sizeof(unsigned long long)));
-
-    MfEvents<3> evs;
-    for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
+    PanelBlocks pb{ctx, fn, src, n_users, n_items, excl_off, excl_item, n_eval, sel.data()};
+    uint64_t* d_held_off = nullptr;
+    uint32_t* d_held_item = nullptr;
+    uint32_t* d_rank = nullptr;    // of every held-out edge
+    uint32_t* d_ncand = nullptr;   // of one block
+    unsigned long long* d_nan_held = nullptr;
+    CF_TRY(pb.begin([&](Carver& c) {
+        d_held_off = c.take<uint64_t>(hoff.size());
+        d_held_item = c.take<uint32_t>(n_held);
+        d_rank = c.take<uint32_t>(n_held);
+        d_ncand = c.take<uint32_t>(pb.ub);
+        d_nan_held = c.take<unsigned long long>(1);
+    }));
+    CF_HIP_CHECK(ctx, hipMemcpy(d_held_off, hoff.data(), sizeof(uint64_t) * hoff.size(), hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemcpy(d_held_item, held_item, sizeof(uint32_t) * n_held, hipMemcpyHostToDevice));
+    CF_HIP_CHECK(ctx, hipMemset(d_nan_held, 0, sizeof(unsigned long long)));
     std::vector<uint32_t> n_cand(n_eval);
-    uint32_t blocks = 0;
-    for (uint32_t b0 = 0; b0 < n_eval; b0 += ub) {
-        const uint32_t nb = std::min(ub, n_eval - b0);
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        CF_TRY(src.fill(ctx, st, (const uint32_t*)L.sel, b0, nb, L.panel));
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
-        const uint64_t edges = nnz ? sel_off[b0 + nb] - sel_off[b0] : 0;
-        if (edges) {
-            if ((edges + kAT - 1) / kAT > 0x7fffffffull)
-                return cf_set_error(ctx, CF_ERANGE, fn + ": exclusions of one user block exceed the launch grid");
-            hipLaunchKernelGGL(topn_exclude_kernel, dim3((unsigned)((edges + kAT - 1) / kAT)), dim3(kAT), 0, st,
-                               (const uint64_t*)L.excl_off, (const uint32_t*)L.excl_item, (const uint64_t*)L.sel_off,
-                               (const uint32_t*)L.sel, b0, nb, n_items, edges, L.panel);
-        }
-        hipLaunchKernelGGL(rank_count_kernel, dim3(nb), dim3(kAT), 0, st, (const uint64_t*)L.panel, n_items,
-                           (const uint64_t*)L.held_off, (const uint32_t*)L.held_item, b0, L.out_rank, L.out_ncand,
-                           L.n_nan_held);
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
-        CF_HIP_CHECK(ctx, hipGetLastError());
-        // the copies wait for the stream
-        CF_HIP_CHECK(ctx, hipMemcpy(rank + hoff[b0], L.out_rank + hoff[b0], sizeof(uint32_t) * (hoff[b0 + nb] - hoff[b0]),
-                                    hipMemcpyDeviceToHost));
-        CF_HIP_CHECK(ctx, hipMemcpy(n_cand.data() + b0, L.out_ncand, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-        float a = 0.0f, b = 0.0f;
-        (void)hipEventElapsedTime(&a, evs.e[0], evs.e[1]);
-        (void)hipEventElapsedTime(&b, evs.e[1], evs.e[2]);
-        score_ms += a;
-        rank_ms += b;
-        ++blocks;
-    }
+    CF_TRY(pb.run(
+        [&](uint32_t b0, uint32_t nb) {
+            hipLaunchKernelGGL(rank_count_kernel, dim3(nb), dim3(kAT), 0, pb.st, (const uint64_t*)pb.d_panel, n_items,
+                               (const uint64_t*)d_held_off, (const uint32_t*)d_held_item, b0, d_rank, d_ncand, d_nan_held);
+        },
+        [&](uint32_t b0, uint32_t nb) {
+            CF_HIP_CHECK(ctx, hipMemcpy(rank + hoff[b0], d_rank + hoff[b0], sizeof(uint32_t) * (hoff[b0 + nb] - hoff[b0]),
+                                        hipMemcpyDeviceToHost));
+            CF_HIP_CHECK(ctx, hipMemcpy(n_cand.data() + b0, d_ncand, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+            return (int)CF_OK;
+        }));
     unsigned long long n_nan_held = 0;
-    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan_held, L.n_nan_held, sizeof(n_nan_held), hipMemcpyDeviceToHost));
+    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan_held, d_nan_held, sizeof(n_nan_held), hipMemcpyDeviceToHost));
 
     // the metrics: a few flops per edge, from the integers alone, in ascending user index
     cf_rank_summary s{};
@@ -343,9 +273,9 @@ int cf_rank_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_us
     if (s.users_auc) s.auc /= (double)s.users_auc;
     s.mpr = pr_den != 0.0 ? pr_num / pr_den : 0.0;
     s.n_nan_held = n_nan_held;
-    s.blocks = blocks;
-    s.score_ms = score_ms;
-    s.rank_ms = rank_ms;
+    s.blocks = pb.blocks;
+    s.score_ms = pb.score_ms;
+    s.rank_ms = pb.use_ms;
     if (summary) *summary = s;
     return CF_OK;
 }

@@ -12,9 +12,10 @@
 //                        (key descending, item ascending), and the keys mapped back to doubles
 // A score's bits do not depend on the tile it falls in, the block size or the other users; the
 // only atomics are integer counts (the LDS histogram, the NaN count).
-// The host driver (cf_topn_drive: checks, workspace, user blocks, exclusion, selection, copies) takes
-// the panel's filler as a PanelSource (cf_internal.h): the factors here, the item graph in
-// cf_knn_topn.hip.
+// The host driver (cf_topn_drive: its checks, the list slots, the selection kernel, the copies back
+// and the stats) takes the panel's filler as a PanelSource (cf_internal.h): the factors here, the
+// item graph in cf_knn_topn.hip, EASE in cf_ease.hip.  The user blocks, their workspace, the uploads
+// and the exclusion launch are PanelBlocks (cf_topn_panel.h), shared with cf_rank_drive.
 
 #include "cf_topn_panel.h"
 
@@ -212,19 +213,6 @@ __global__ __launch_bounds__(kAT) void topn_select_kernel(const uint64_t* __rest
     }
 }
 
-struct TopnLayout {
-    void* src;   // the score source's part (PanelSource::workspace)
-    uint64_t* excl_off;
-    uint32_t* excl_item;
-    uint64_t* sel_off;
-    uint32_t* sel;
-    uint64_t* panel;
-    uint32_t* out_items;
-    double* out_scores;
-    uint32_t* out_count;
-    unsigned long long* n_nan;
-};
-
 }  // namespace
 
 extern "C" int cf_debug_topn_tile_users(void) { return kTU; }
@@ -256,10 +244,7 @@ int cf_topn_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_us
                   const uint64_t* excl_off, const uint32_t* excl_item, uint32_t n_sel, const uint32_t* sel_user,
                   uint32_t N, uint32_t* items, double* scores, uint32_t* count, cf_topn_stats* stats) {
     const std::string fn = name;
-    if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
-    if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
-    if ((excl_off == nullptr) != (excl_item == nullptr))
-        return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
+    CF_TRY(panel_check_head(ctx, fn, N, excl_off, excl_item));
     const uint32_t n_out = sel_user ? n_sel : n_users;
     if (sel_user)
         for (uint32_t j = 0; j < n_sel; ++j)
@@ -272,88 +257,36 @@ int cf_topn_drive(cf_ctx* ctx, const char* name, PanelSource& src, uint32_t n_us
     if (!src.valid() || !items || !scores) return cf_set_error(ctx, CF_EINVAL, fn + ": null argument");
     CF_TRY(set_device(ctx));
 
-    const uint64_t nnz = excl_off ? excl_off[n_users] : 0;
-    // the selection's own prefix of exclusion counts; without a selection it is excl_off
-    std::vector<uint64_t> sel_off;
-    if (sel_user && nnz) {
-        sel_off.assign((size_t)n_sel + 1, 0);
-        for (uint32_t j = 0; j < n_sel; ++j)
-            sel_off[j + 1] = sel_off[j] + (excl_off[sel_user[j] + 1] - excl_off[sel_user[j]]);
-    }
-    const uint32_t ub = topn_block_users(ctx, n_items, n_out);
-    const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
-    if ((uint64_t)((ub + kTU - 1) / kTU) * n_it > 0x7fffffffull)
-        return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
-
-    TopnLayout L{};
-    const size_t src_bytes = src.workspace(ub);
-    for (int pass = 0; pass < 2; ++pass) {
-        Carver c;
-        if (pass) c.base = static_cast<char*>(ctx->d_als);
-        L.src = c.take<char>(src_bytes);
-        L.excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
-        L.excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
-        L.sel_off = !sel_off.empty() ? c.take<uint64_t>(sel_off.size()) : nullptr;
-        L.sel = sel_user ? c.take<uint32_t>(n_sel) : nullptr;
-        L.panel = c.take<uint64_t>((size_t)ub * n_items);
-        L.out_items = c.take<uint32_t>((size_t)ub * N);
-        L.out_scores = c.take<double>((size_t)ub * N);
-        L.out_count = c.take<uint32_t>(ub);
-        L.n_nan = c.take<unsigned long long>(1);
-        if (!pass) CF_TRY(als_reserve(ctx, c.pos));
-    }
-    hipStream_t st = nullptr;
-    float score_ms = 0.0f, select_ms = 0.0f;
-    CF_TRY(src.upload(ctx, L.src, ub, st, &score_ms));
-    if (nnz) {
-        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
-        CF_HIP_CHECK(ctx, hipMemcpy(L.excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
-    }
-    if (L.sel_off)
-        CF_HIP_CHECK(ctx, hipMemcpy(L.sel_off, sel_off.data(), sizeof(uint64_t) * sel_off.size(), hipMemcpyHostToDevice));
-    if (sel_user) CF_HIP_CHECK(ctx, hipMemcpy(L.sel, sel_user, sizeof(uint32_t) * n_sel, hipMemcpyHostToDevice));
-    CF_HIP_CHECK(ctx, hipMemset(L.n_nan, 0, sizeof(unsigned long long)));
-
-    MfEvents<3> evs;
-    for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
-    const uint64_t* d_sel_off = L.sel_off ? L.sel_off : L.excl_off;
-    const uint64_t* h_sel_off = !sel_off.empty() ? sel_off.data() : excl_off;
-    uint32_t blocks = 0;
-    for (uint32_t b0 = 0; b0 < n_out; b0 += ub) {
-        const uint32_t nb = std::min(ub, n_out - b0);
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
-        CF_TRY(src.fill(ctx, st, (const uint32_t*)L.sel, b0, nb, L.panel));
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
-        const uint64_t edges = nnz ? h_sel_off[b0 + nb] - h_sel_off[b0] : 0;
-        if (edges) {
-            if ((edges + kAT - 1) / kAT > 0x7fffffffull)
-                return cf_set_error(ctx, CF_ERANGE, fn + ": exclusions of one user block exceed the launch grid");
-            hipLaunchKernelGGL(topn_exclude_kernel, dim3((unsigned)((edges + kAT - 1) / kAT)), dim3(kAT), 0, st,
-                               (const uint64_t*)L.excl_off, (const uint32_t*)L.excl_item, d_sel_off,
-                               (const uint32_t*)L.sel, b0, nb, n_items, edges, L.panel);
-        }
-        hipLaunchKernelGGL(topn_select_kernel, dim3(nb), dim3(kAT), 0, st, (const uint64_t*)L.panel, n_items, N,
-                           L.out_items, L.out_scores, L.out_count, L.n_nan);
-        CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
-        CF_HIP_CHECK(ctx, hipGetLastError());
-        // the copies wait for the stream
-        CF_HIP_CHECK(ctx, hipMemcpy(items + (size_t)b0 * N, L.out_items, sizeof(uint32_t) * (size_t)nb * N, hipMemcpyDeviceToHost));
-        CF_HIP_CHECK(ctx, hipMemcpy(scores + (size_t)b0 * N, L.out_scores, sizeof(double) * (size_t)nb * N, hipMemcpyDeviceToHost));
-        CF_HIP_CHECK(ctx, hipMemcpy(count + b0, L.out_count, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-        float a = 0.0f, b = 0.0f;
-        (void)hipEventElapsedTime(&a, evs.e[0], evs.e[1]);
-        (void)hipEventElapsedTime(&b, evs.e[1], evs.e[2]);
-        score_ms += a;
-        select_ms += b;
-        ++blocks;
-    }
+    PanelBlocks pb{ctx, fn, src, n_users, n_items, excl_off, excl_item, n_out, sel_user};
+    uint32_t* d_items = nullptr;   // the lists of one block
+    double* d_scores = nullptr;
+    uint32_t* d_count = nullptr;
+    unsigned long long* d_nan = nullptr;
+    CF_TRY(pb.begin([&](Carver& c) {
+        d_items = c.take<uint32_t>((size_t)pb.ub * N);
+        d_scores = c.take<double>((size_t)pb.ub * N);
+        d_count = c.take<uint32_t>(pb.ub);
+        d_nan = c.take<unsigned long long>(1);
+    }));
+    CF_HIP_CHECK(ctx, hipMemset(d_nan, 0, sizeof(unsigned long long)));
+    CF_TRY(pb.run(
+        [&](uint32_t, uint32_t nb) {
+            hipLaunchKernelGGL(topn_select_kernel, dim3(nb), dim3(kAT), 0, pb.st, (const uint64_t*)pb.d_panel, n_items, N,
+                               d_items, d_scores, d_count, d_nan);
+        },
+        [&](uint32_t b0, uint32_t nb) {
+            CF_HIP_CHECK(ctx, hipMemcpy(items + (size_t)b0 * N, d_items, sizeof(uint32_t) * (size_t)nb * N, hipMemcpyDeviceToHost));
+            CF_HIP_CHECK(ctx, hipMemcpy(scores + (size_t)b0 * N, d_scores, sizeof(double) * (size_t)nb * N, hipMemcpyDeviceToHost));
+            CF_HIP_CHECK(ctx, hipMemcpy(count + b0, d_count, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+            return (int)CF_OK;
+        }));
     unsigned long long n_nan = 0;
-    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan, L.n_nan, sizeof(n_nan), hipMemcpyDeviceToHost));
+    CF_HIP_CHECK(ctx, hipMemcpy(&n_nan, d_nan, sizeof(n_nan), hipMemcpyDeviceToHost));
     if (stats) {
-        stats->blocks = blocks;
+        stats->blocks = pb.blocks;
         stats->n_nan = n_nan;
-        stats->score_ms = score_ms;
-        stats->select_ms = select_ms;
+        stats->score_ms = pb.score_ms;
+        stats->select_ms = pb.use_ms;
     }
     return CF_OK;
 }

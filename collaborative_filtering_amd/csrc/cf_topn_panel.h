@@ -1,9 +1,10 @@
 // cf_topn_panel.h -- the score panel that cf_topn.hip (the N best items per user) and cf_rank.hip
 // (the rank of held-out items) share: the order-preserving 64-bit key of a score, the kernel that
 // scores a block of users into a panel of keys, the kernel that marks the excluded pairs in it, the
-// row walk's loads, the order of two (key, item) pairs, the users-per-block rule and the factor
-// source of the panel drivers (MfPanelSource; cf_knn_topn.hip has the graph source, cf_ease.hip
-// the EASE one).
+// row walk's loads, the order of two (key, item) pairs, the users-per-block rule, the factor source
+// of the panel drivers (MfPanelSource), the part of both drivers up to a filled and excluded block
+// (panel_check_head, PanelBlocks) and the base of the sources that score from user profiles
+// (ProfilePanelSource: the graph source of cf_knn_topn.hip, the EASE one of cf_ease.hip).
 //
 // The selected users run in blocks of `ub` users whose scores live in a panel of 64-bit keys,
 // key[user in block][item] (row stride n_items, carved from the context's ALS workspace):
@@ -223,6 +224,151 @@ struct MfPanelSource final : PanelSource {
         hipLaunchKernelGGL(topn_score_kernel, dim3(tiles), dim3(kAT), 0, st, (const double*)dU, (const double*)dV, (int)D,
                            n_items, n_it, d_sel, b0, nb, (const double*)dbu, (const double*)dbi, bias_mean, d_panel);
         return CF_OK;
+    }
+};
+
+// The first checks of both panel drivers, in their order.
+inline int panel_check_head(cf_ctx* ctx, const std::string& fn, uint32_t N, const uint64_t* excl_off,
+                            const uint32_t* excl_item) {
+    if (N > CF_TOPN_MAX_N) return cf_set_error(ctx, CF_ERANGE, fn + ": N above CF_TOPN_MAX_N");
+    if (N == 0) return cf_set_error(ctx, CF_EINVAL, fn + ": N = 0");
+    if ((excl_off == nullptr) != (excl_item == nullptr))
+        return cf_set_error(ctx, CF_EINVAL, fn + ": exactly one of excl_off / excl_item is null");
+    return CF_OK;
+}
+
+// The user blocks of both panel drivers (cf_topn_drive, cf_rank_drive), after their checks: the
+// n_out users of the selection (sel_user on the host; null = users 0 .. n_out - 1) run in blocks
+// of ub, each filled by src and stripped of its exclusions; what is done with a filled block is
+// the caller's.  begin() sizes the blocks, carves the workspace (own(Carver&) adds the caller's
+// arrays to the same carve, once per pass) and uploads source, exclusions and selection; run()
+// is the loop: per block launch(b0, nb) between the events, then collect(b0, nb) -> int with the
+// copies back, which wait for the stream.  score_ms: the fills (and what the source's upload
+// adds), use_ms: exclusion and launch().
+struct PanelBlocks {
+    cf_ctx* ctx;
+    std::string fn;
+    PanelSource& src;
+    uint32_t n_users, n_items;
+    const uint64_t* excl_off;
+    const uint32_t* excl_item;
+    uint32_t n_out;
+    const uint32_t* sel_user;
+
+    uint32_t ub = 0, blocks = 0;
+    uint64_t nnz = 0;
+    std::vector<uint64_t> sel_off;   // the selection's own prefix of exclusion counts; without a selection it is excl_off
+    uint64_t* d_excl_off = nullptr;
+    uint32_t* d_excl_item = nullptr;
+    uint64_t* d_sel_off = nullptr;
+    uint32_t* d_sel = nullptr;
+    uint64_t* d_panel = nullptr;
+    hipStream_t st = nullptr;
+    float score_ms = 0.0f, use_ms = 0.0f;
+
+    template <class Own>
+    int begin(Own own) {
+        nnz = excl_off ? excl_off[n_users] : 0;
+        if (sel_user && nnz) {
+            sel_off.assign((size_t)n_out + 1, 0);
+            for (uint32_t j = 0; j < n_out; ++j)
+                sel_off[j + 1] = sel_off[j] + (excl_off[sel_user[j] + 1] - excl_off[sel_user[j]]);
+        }
+        ub = topn_block_users(ctx, n_items, n_out);
+        const uint32_t n_it = (uint32_t)(((uint64_t)n_items + kTI - 1) / kTI);
+        if ((uint64_t)((ub + kTU - 1) / kTU) * n_it > 0x7fffffffull)
+            return cf_set_error(ctx, CF_ERANGE, fn + ": users per block x items exceed the launch grid");
+        void* d_src = nullptr;
+        const size_t src_bytes = src.workspace(ub);
+        CF_TRY(carve_workspace(ctx, [&](Carver& c) {
+            d_src = c.take<char>(src_bytes);
+            d_excl_off = nnz ? c.take<uint64_t>((size_t)n_users + 1) : nullptr;
+            d_excl_item = nnz ? c.take<uint32_t>(nnz) : nullptr;
+            d_sel_off = !sel_off.empty() ? c.take<uint64_t>(sel_off.size()) : nullptr;
+            d_sel = sel_user ? c.take<uint32_t>(n_out) : nullptr;
+            d_panel = c.take<uint64_t>((size_t)ub * n_items);
+            own(c);
+        }));
+        CF_TRY(src.upload(ctx, d_src, ub, st, &score_ms));
+        if (nnz) {
+            CF_HIP_CHECK(ctx, hipMemcpy(d_excl_off, excl_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
+            CF_HIP_CHECK(ctx, hipMemcpy(d_excl_item, excl_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+        }
+        if (d_sel_off)
+            CF_HIP_CHECK(ctx, hipMemcpy(d_sel_off, sel_off.data(), sizeof(uint64_t) * sel_off.size(), hipMemcpyHostToDevice));
+        if (sel_user) CF_HIP_CHECK(ctx, hipMemcpy(d_sel, sel_user, sizeof(uint32_t) * n_out, hipMemcpyHostToDevice));
+        return CF_OK;
+    }
+
+    template <class Launch, class Collect>
+    int run(Launch launch, Collect collect) {
+        MfEvents<3> evs;
+        for (hipEvent_t& e : evs.e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
+        const uint64_t* dev_off = d_sel_off ? d_sel_off : d_excl_off;
+        const uint64_t* host_off = !sel_off.empty() ? sel_off.data() : excl_off;
+        for (uint32_t b0 = 0; b0 < n_out; b0 += ub) {
+            const uint32_t nb = std::min(ub, n_out - b0);
+            CF_HIP_CHECK(ctx, hipEventRecord(evs.e[0], st));
+            CF_TRY(src.fill(ctx, st, (const uint32_t*)d_sel, b0, nb, d_panel));
+            CF_HIP_CHECK(ctx, hipEventRecord(evs.e[1], st));
+            const uint64_t edges = nnz ? host_off[b0 + nb] - host_off[b0] : 0;
+            if (edges) {
+                if ((edges + kAT - 1) / kAT > 0x7fffffffull)
+                    return cf_set_error(ctx, CF_ERANGE, fn + ": exclusions of one user block exceed the launch grid");
+                hipLaunchKernelGGL(topn_exclude_kernel, dim3((unsigned)((edges + kAT - 1) / kAT)), dim3(kAT), 0, st,
+                                   (const uint64_t*)d_excl_off, (const uint32_t*)d_excl_item, dev_off, (const uint32_t*)d_sel,
+                                   b0, nb, n_items, edges, d_panel);
+            }
+            launch(b0, nb);
+            CF_HIP_CHECK(ctx, hipEventRecord(evs.e[2], st));
+            CF_HIP_CHECK(ctx, hipGetLastError());
+            CF_TRY(collect(b0, nb));
+            score_ms += elapsed(evs.e[0], evs.e[1]);
+            use_ms += elapsed(evs.e[1], evs.e[2]);
+            ++blocks;
+        }
+        return CF_OK;
+    }
+};
+
+// What the sources that score from user profiles share (the graph in cf_knn_topn.hip, EASE in
+// cf_ease.hip): the profile CSR on the host, checked by the entry point, and its copy at the head
+// of the source's workspace.
+struct ProfilePanelSource : PanelSource {
+    uint32_t n_users = 0, n_items = 0;
+    const uint64_t* prof_off = nullptr;
+    const uint32_t* prof_item = nullptr;
+    const float* prof_rating = nullptr;
+    struct Dev {
+        uint64_t* off;
+        uint32_t* item;
+        float* rating;
+    } dev{};
+
+    Dev carve(Carver& c) const {
+        const uint64_t nnz = prof_off[n_users];
+        return Dev{c.take<uint64_t>((size_t)n_users + 1), c.take<uint32_t>(nnz), c.take<float>(nnz)};
+    }
+    int upload_profiles(cf_ctx* ctx, Carver& c) {
+        dev = carve(c);
+        const uint64_t nnz = prof_off[n_users];
+        CF_HIP_CHECK(ctx, hipMemcpy(dev.off, prof_off, sizeof(uint64_t) * ((size_t)n_users + 1), hipMemcpyHostToDevice));
+        if (nnz) {
+            CF_HIP_CHECK(ctx, hipMemcpy(dev.item, prof_item, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+            CF_HIP_CHECK(ctx, hipMemcpy(dev.rating, prof_rating, sizeof(float) * nnz, hipMemcpyHostToDevice));
+        }
+        return CF_OK;
+    }
+    bool valid() const override { return true; }
+    size_t workspace(uint32_t) const override {
+        Carver c;
+        carve(c);
+        return c.pos;
+    }
+    int upload(cf_ctx* ctx, void* ws, uint32_t, hipStream_t, float*) override {
+        Carver c;
+        c.base = static_cast<char*>(ws);
+        return upload_profiles(ctx, c);
     }
 };
 

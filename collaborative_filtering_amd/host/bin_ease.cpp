@@ -91,21 +91,15 @@ int main(int argc, char** argv) {
         em.insert(em.end(), d.em[cfio::kValidate].begin(), d.em[cfio::kValidate].end());
         cfmf::Csr excl = cfmf::build_csr(nu, eu, em, std::vector<float>(eu.size(), 0.0f));
         if (excl.nbr.empty()) excl.nbr.push_back(0);
-        std::vector<uint32_t> sel;
-        const bool selected = !users_file.empty();
-        if (selected) sel = cfrank::read_users(users_file, d.uids, matrix);
-        const uint32_t n_out = selected ? (uint32_t)sel.size() : nu;
-        if (selected && sel.empty()) sel.push_back(0);
-        std::vector<uint32_t> items((size_t)n_out * N), count(n_out);
-        std::vector<double> scores((size_t)n_out * N);
+        cfrank::Lists l = cfrank::make_lists(users_file, d.uids, matrix, nu, N);
         cf_topn_stats st{};
         cfcli::check(ctx,
                      cf_ease_topn(ctx, nu, prof.off.data(), prof.nbr.data(), prof.obs.data(), binary ? 1 : 0,
-                                  excl.off.data(), excl.nbr.data(), selected ? n_out : 0, selected ? sel.data() : nullptr, N,
-                                  items.data(), scores.data(), count.data(), &st),
+                                  excl.off.data(), excl.nbr.data(), l.n_sel(), l.sel_ptr(), N, l.items.data(),
+                                  l.scores.data(), l.count.data(), &st),
                      "cf_ease_topn");
         cfrank::print_topn_stats(st);
-        cfrank::write_lists(recommend, nshards, d.uids, d.mids, selected, sel, n_out, N, items, scores, count);
+        cfrank::write_lists(recommend, nshards, d.uids, d.mids, l);
     }
 
     if (rankeval) {

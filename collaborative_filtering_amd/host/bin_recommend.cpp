@@ -20,9 +20,6 @@
 #include <cstdio>
 #include <cstring>
 
-#include "cf_factor_io.hpp"
-#include "cf_knn_cli.hpp"
-#include "cf_mf_cli.hpp"
 #include "cf_rank_cli.hpp"
 
 int main(int argc, char** argv) {
@@ -44,79 +41,38 @@ int main(int argc, char** argv) {
     if (N == 0 || N > CF_TOPN_MAX_N) cfcli::die("--topn must be between 1 and " + std::to_string(CF_TOPN_MAX_N));
     if (nshards < 1) cfcli::die("--nshards must be at least 1");
 
-    const bool from_graph = !knn.graph.empty();
-    cf_ctx* ctx = nullptr;
-    cfmf::Factors fu, fv;
-    cfknn::Source g;
-    std::vector<double> bu, bi;
-    if (from_graph) {
-        ctx = cfcli::open_device();
-        g = cfknn::load(ctx, knn.graph, matrix);
-    } else {
-        fu = cfmf::read_factors(factors + ".U");
-        fv = cfmf::read_factors(factors + ".V");
-        if (fu.width != fv.width)
-            cfcli::die("factor line of another width: " + factors + ".U holds " + std::to_string(fu.width) +
-                       " values per line, " + factors + ".V " + std::to_string(fv.width));
-        if (fu.width > CF_ALS_MAX_D)
-            cfcli::die("D = " + std::to_string(fu.width) + " is above " + std::to_string(CF_ALS_MAX_D));
-        if (bias) {
-            bu = cfmf::read_bias(factors + ".bias.U", fu);
-            bi = cfmf::read_bias(factors + ".bias.V", fv);
-        }
-    }
-    const cfio::IdMap& uids = from_graph ? g.users : fu.ids;
-    const cfio::IdMap& mids = from_graph ? g.items : fv.ids;
-    const std::string ufile = from_graph ? matrix : factors + ".U_*";   // where a user id comes from
-    const uint32_t D = fu.width, nu = uids.size(), nm = mids.size();
+    cfrank::Source src;
+    cfrank::load_source(src, knn, factors, matrix, bias);
+    const cfio::IdMap &uids = src.uids(), &mids = src.mids();
+    const uint32_t nu = uids.size(), nm = mids.size();
 
-    // exclusions: the TRAIN and VALIDATE edges, as a CSR by user
+    // exclusions: the TRAIN and VALIDATE edges
     cfmf::Csr excl;
-    if (!matrix.empty()) {
-        std::vector<uint32_t> eu, em;
-        for (const cfio::RoleRating& r : from_graph ? g.roles : cfio::load_movielens_roles(matrix)) {
-            const auto u = uids.at.find(r.user);
-            if (u == uids.at.end())
-                cfcli::die("user " + std::to_string(r.user) + " of " + matrix + " has no line in " + factors + ".U_*");
-            const auto m = mids.at.find(r.item);
-            if (m == mids.at.end())
-                cfcli::die("item " + std::to_string(r.item) + " of " + matrix + " has no line in " + factors + ".V_*");
-            if (r.role == cfio::kPredict) continue;
-            eu.push_back(u->second);
-            em.push_back(m->second);
-        }
-        excl = cfmf::build_csr(nu, eu, em, std::vector<float>(eu.size(), 0.0f));
-        if (excl.nbr.empty()) excl.nbr.push_back(0);   // a valid pointer for an empty list
-    }
+    if (!matrix.empty())
+        excl = cfrank::role_exclusions(src, matrix, factors, 1u << cfio::kTrain | 1u << cfio::kValidate, nullptr);
+    // where a user id comes from
+    cfrank::Lists l = cfrank::make_lists(users_file, uids, src.from_graph ? matrix : factors + ".U_*", nu, N);
 
-    std::vector<uint32_t> sel;
-    if (!users_file.empty()) sel = cfrank::read_users(users_file, uids, ufile);
-    const bool selected = !users_file.empty();
-    const uint32_t n_out = selected ? (uint32_t)sel.size() : nu;
-    if (selected && sel.empty()) sel.push_back(0);
-
-    if (from_graph) std::printf("Users: %u items: %u\n", nu, nm);
-    else std::printf("Users: %u items: %u D: %u\n", nu, nm, D);
-    std::vector<uint32_t> items((size_t)n_out * N), count(n_out);
-    std::vector<double> scores((size_t)n_out * N);
+    src.print_sizes();
     cf_topn_stats st{};
-    if (from_graph) {
-        cfcli::check(ctx,
-                     cf_knn_topn(ctx, nu, g.profile.off.data(), g.profile.nbr.data(), g.profile.obs.data(), knn.score_mode,
-                                 knn.w_min, excl.off.data(), excl.nbr.data(), selected ? n_out : 0,
-                                 selected ? sel.data() : nullptr, N, items.data(), scores.data(), count.data(), &st),
+    if (src.from_graph) {
+        const cfmf::Csr& prof = src.g.profile;
+        cfcli::check(src.ctx,
+                     cf_knn_topn(src.ctx, nu, prof.off.data(), prof.nbr.data(), prof.obs.data(), knn.score_mode, knn.w_min,
+                                 excl.off.data(), excl.nbr.data(), l.n_sel(), l.sel_ptr(), N, l.items.data(),
+                                 l.scores.data(), l.count.data(), &st),
                      "cf_knn_topn");
     } else {
-        ctx = cfcli::open_device();
-        cfcli::check(ctx,
-                     cf_mf_topn(ctx, nu, nm, D, fu.F.data(), fv.F.data(), bias ? bu.data() : nullptr,
-                                bias ? bi.data() : nullptr, mean, matrix.empty() ? nullptr : excl.off.data(),
-                                matrix.empty() ? nullptr : excl.nbr.data(), selected ? n_out : 0,
-                                selected ? sel.data() : nullptr, N, items.data(), scores.data(), count.data(), &st),
+        src.ctx = cfcli::open_device();
+        cfcli::check(src.ctx,
+                     cf_mf_topn(src.ctx, nu, nm, src.fu.width, src.fu.F.data(), src.fv.F.data(),
+                                bias ? src.bu.data() : nullptr, bias ? src.bi.data() : nullptr, mean,
+                                matrix.empty() ? nullptr : excl.off.data(), matrix.empty() ? nullptr : excl.nbr.data(),
+                                l.n_sel(), l.sel_ptr(), N, l.items.data(), l.scores.data(), l.count.data(), &st),
                      "cf_mf_topn");
     }
     cfrank::print_topn_stats(st);
-    cfrank::write_lists(output, nshards, uids, mids, selected, sel, n_out, N, items, scores, count);
-    cf_destroy(ctx);
+    cfrank::write_lists(output, nshards, uids, mids, l);
+    cf_destroy(src.ctx);
     return 0;
 }

@@ -183,7 +183,10 @@ def _init(seed, nu, ni, D, bias=True):
 
 D_SWEEP = (1, 5, 20, 33, 64)
 NO_BIAS = "D20"
-CASES = ("P",) + tuple(f"D{d}" for d in D_SWEEP) + ("M", "N", "E")
+# name: (n_items, edges, seed): edges and n_items + 1 = 256 and 257; the seeds draw no negative at
+# item 0 or at the last item in sweep 0 (test_bpr_ref.py)
+T_CASES = {"T256": (255, 256, 1), "T257": (256, 257, 1)}
+CASES = ("P",) + tuple(f"D{d}" for d in D_SWEEP) + ("M", "N", "E") + tuple(T_CASES)
 SEG, LOW = 2048, 64   # the cuts the cases are built around; test_bpr_ref.py checks them against the library
 
 
@@ -215,6 +218,14 @@ def _make(name) -> Case:
         user, item = sort_pairs(user, item)
         U0, V0, b0 = _init(15, nu, ni, 3)
         return Case(nu, ni, 3, user, item, U0, V0, b0, 2, 1.0, 0.01, 8)
+    if name in T_CASES:   # the negative lists at the edges of the 256-thread workgroups that build them
+        ni, nnz, seed = T_CASES[name]
+        rng = np.random.default_rng(16)
+        nu = 200
+        flat = np.sort(rng.choice(nu * (ni - 2), nnz, replace=False))   # items 0 and ni - 1 have no edge
+        user, item = sort_pairs(flat // (ni - 2), flat % (ni - 2) + 1)
+        U0, V0, b0 = _init(17, nu, ni, 4)
+        return Case(nu, ni, 4, user, item, U0, V0, b0, 2, 1.0, 0.01, seed)
     raise KeyError(name)
 
 

@@ -96,6 +96,17 @@ def test_structure_of_m_n_and_e():
     assert np.any(~re_.item_counted) and np.any(~re_.user_counted)    # never in any triple
 
 
+@pytest.mark.parametrize("name", br.T_CASES)
+def test_t_cases_sit_on_the_workgroup_edges(name):
+    """256 threads build the negative lists: one per edge (the positions) and one per offset."""
+    c = br.case_inputs(name)
+    assert (len(c.user), c.n_items + 1) in ((256, 256), (257, 257))
+    assert c.item.min() > 0 and c.item.max() < c.n_items - 1
+    neg = [br.sample(c.user, c.item, c.n_users, c.n_items, c.seed, s) for s in range(c.n_sweeps)]
+    assert not np.isin([0, c.n_items - 1], neg[0]).any()   # empty first and last lists
+    assert np.isin([0, c.n_items - 1], neg[1]).all()       # and filled ones
+
+
 @pytest.mark.parametrize("name", br.CASES)
 def test_no_case_has_nan_and_counts_add_up(name):
     c, r = br.case_inputs(name), br.case_reference(name)

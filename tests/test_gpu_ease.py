@@ -62,6 +62,21 @@ def test_gram_bytes_and_symmetry(gpu_ctx, kind, binary):
     assert same_bytes(gpu_ctx.ease_gram(np.zeros(1, np.uint64), [], [], 5, 2.0), 2.0 * np.eye(5))
 
 
+@pytest.mark.parametrize("nnz", [T, T + 1])
+@pytest.mark.parametrize("n", [T - 1, T])
+def test_gram_bytes_at_the_by_item_workgroup_edges(gpu_ctx, n, nnz):
+    """The by-item lists come from T threads per workgroup, one per edge and one per offset (n + 1 of
+    them): both counts at T and T + 1, items 0 and n - 1 without an edge."""
+    rng = np.random.default_rng(12)
+    flat = np.sort(rng.choice(200 * (n - 2), nnz, replace=False))
+    off = np.searchsorted(flat // (n - 2), np.arange(201)).astype(np.uint64)
+    items = (flat % (n - 2) + 1).astype(np.uint32)
+    ratings = rng.integers(1, 6, nnz).astype(np.float32)
+    want = er.gram(off, items, ratings, n, 0.3, False)
+    assert want[0, 0] == 0.3 and want[n - 1, n - 1] == 0.3 and np.count_nonzero(np.diag(want) > 0.3) > n // 2
+    assert same_bytes(gpu_ctx.ease_gram(off, items, ratings, n, 0.3), want)
+
+
 # ---- fit accuracy ----------------------------------------------------------------------------------
 FIT_SHAPES = ["one", "two", "b_minus_1", "b", "b_plus_1", "two_b_plus_3", "few_users", "few_users_binary"]
 
