@@ -36,6 +36,11 @@ CF_GRAPH_DENSE = 0
 CF_GRAPH_CSR = 1
 CF_FILTER_CHEBY = 0
 CF_FILTER_BINOMIAL = 1
+CF_SPLIT_LEAVE_K = 0
+CF_SPLIT_RATIO = 1
+CF_SPLIT_FOLDS = 2
+CF_SPLIT_DROPPED = 255
+CF_SPLIT_STATS = 8
 
 # name -> (restype, argtypes); the list is the ABI contract checked by tests.
 SIGNATURES = {
@@ -111,6 +116,16 @@ SIGNATURES = {
     "cf_knn_regroup_run": (c_int, [c_void_p, c_uint64, c_uint32, c_uint32] + [c_void_p] * 12 + [c_uint64, c_void_p]),
     "cf_fold_order": (c_int, [c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
     "cf_fold_order_run": (c_int, [c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cf_kcore": (c_int, [c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p,
+                         POINTER(c_uint32)]),
+    "cf_kcore_run": (c_int, [c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p,
+                             POINTER(c_uint32), c_void_p]),
+    "cf_holdout_split": (c_int, [c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64,
+                                 c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "cf_holdout_split_run": (c_int, [c_void_p, c_uint64, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64,
+                                     c_uint32, c_uint32, c_int, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p,
+                                     c_void_p]),
+    "cf_split_timing": (c_int, [c_void_p, c_void_p]),
     "cf_prep_timing": (c_int, [c_void_p, c_void_p]),
     "cf_set_knn2_chunk": (c_int, [c_void_p, c_uint32]),
     "cf_knn2_chunks": (c_int, [c_void_p, c_void_p]),

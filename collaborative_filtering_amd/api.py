@@ -229,6 +229,24 @@ class TopnResult:
     stats: "_native.TopnStats"
 
 
+@dataclass
+class SplitResult:
+    """Outcome of Context.holdout_split: part[i] of the i-th edge read (0 TRAIN, 1 VALIDATE, or the fold
+    number; CF_SPLIT_DROPPED = 255 for a repeated pair's earlier lines and for edges outside the core)
+    and the cf_holdout_split stats as named fields.  In the folds mode train / validate count the
+    edges of folds 0 and 1 and items_without_train is 0."""
+
+    part: np.ndarray   # uint8[n], read order
+    kept: int                  # edges left after duplicates
+    alive: int                 # edges alive after the core
+    users_alive: int
+    items_alive: int
+    train: int
+    validate: int
+    items_without_train: int   # alive items whose every alive edge was held out
+    rounds: int                # core rounds in which an edge died
+
+
 # cf_rank_user (cf_abi.h) as a numpy record: the per-user arrays of RankEvalResult are its fields
 RANK_USER_DTYPE = np.dtype([("n_cand", np.uint32), ("n_rel", np.uint32), ("hits", np.uint32), ("reserved", np.uint32),
                             ("precision", np.float64), ("recall", np.float64), ("ndcg", np.float64),
@@ -696,8 +714,57 @@ class Context:
                   "cf_fold_order")
         return order[:len(user)]
 
+    # -- per-user hold-out split and k-core filter (cf_split.hip) ----------------------------------
+    def kcore(self, n_users, n_items, user, item, min_user=0, min_item=0):
+        """(keep bool[n] in read order, rounds): the last edge read of every (user, item) that lies in
+        the (min_user, min_item) core of the bipartite graph (cf_kcore; 0 or 1: no limit)."""
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        if len(user) != len(item):
+            raise ValueError("user and item differ in length")
+        keep = np.zeros(max(len(user), 1), np.uint8)
+        rounds = c_uint32()
+        self._chk(self.lib.cf_kcore(self.h, len(user), int(n_users), int(n_items), ptr(user), ptr(item), int(min_user),
+                                    int(min_item), ptr(keep), byref(rounds)), "cf_kcore")
+        return keep[:len(user)].astype(bool), rounds.value
+
+    def holdout_split(self, n_users, n_items, user, item, *, holdout=None, ratio=None, folds=None, order_key=None,
+                      seed=0, min_train=0, min_user=0, min_item=0) -> SplitResult:
+        """Per-user split of the edges (read order, compact ids) after dropping repeated pairs and the
+        (min_user, min_item) core filter (cf_holdout_split).  Exactly one of holdout=K (leave K out),
+        ratio=(num, den) and folds=F.  Within a user the edges are ordered by (order_key, item); without
+        order_key the key is a hash of (seed, user, item), so the split does not depend on the read
+        order.  The core runs before the hold-out: a TRAIN degree may end below the core's limit."""
+        if (holdout is not None) + (ratio is not None) + (folds is not None) != 1:
+            raise ValueError("exactly one of holdout, ratio and folds")
+        if holdout is not None:
+            mode, a, b = _native.CF_SPLIT_LEAVE_K, int(holdout), 0
+        elif ratio is not None:
+            mode, a, b = _native.CF_SPLIT_RATIO, int(ratio[0]), int(ratio[1])
+        else:
+            mode, a, b = _native.CF_SPLIT_FOLDS, int(folds), 0
+        user = np.ascontiguousarray(user, dtype=np.uint32)
+        item = np.ascontiguousarray(item, dtype=np.uint32)
+        key = None if order_key is None else np.ascontiguousarray(order_key, dtype=np.uint64)
+        if len(user) != len(item) or (key is not None and len(key) != len(user)):
+            raise ValueError("user, item and order_key differ in length")
+        part = np.zeros(max(len(user), 1), np.uint8)
+        stats = np.zeros(_native.CF_SPLIT_STATS, np.uint64)
+        self._chk(self.lib.cf_holdout_split(self.h, len(user), int(n_users), int(n_items), ptr(user), ptr(item),
+                                            ptr(key) if key is not None else None, int(seed), int(min_user),
+                                            int(min_item), mode, a, b, int(min_train), ptr(part), ptr(stats)),
+                  "cf_holdout_split")
+        return SplitResult(part[:len(user)], *(int(s) for s in stats))
+
+    def split_timing(self):
+        """Device ms of the last kcore / holdout_split by step: (keys + sort + lists, core rounds, order
+        sorts, parts + stats)."""
+        ms = (c_float * 4)()
+        self._chk(self.lib.cf_split_timing(self.h, ms), "cf_split_timing")
+        return tuple(ms)
+
     def prep_timing(self):
-        """Device ms of the last regroup / fold-order call (HIP events)."""
+        """Device ms of the last regroup / fold-order / kcore / holdout-split call (HIP events)."""
         t = c_float()
         self._chk(self.lib.cf_prep_timing(self.h, byref(t)), "cf_prep_timing")
         return t.value

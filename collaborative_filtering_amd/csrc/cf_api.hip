@@ -166,6 +166,8 @@ void cf_destroy(cf_ctx* ctx) {
     if (ctx->d_als) (void)hipFree(ctx->d_als);
     for (hipEvent_t& e : ctx->prep_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t& e : ctx->split_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto& run : ctx->bucket_ev)
         for (auto& pr : run)
             for (hipEvent_t& e : pr)

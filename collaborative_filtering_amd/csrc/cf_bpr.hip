@@ -42,18 +42,12 @@
 #include "cf_internal.h"
 #include "cf_mf_reduce.h"
 #include "cf_sort.h"
+#include "cf_splitmix.h"   // splitmix64
 
 namespace {
 
 constexpr uint32_t kSkipped = 0xffffffffu;
 static_assert(CF_BPR_TRIES == kG, "one lane of an edge's group per try");
-
-__host__ __device__ inline uint64_t splitmix64(uint64_t x) {   // host/cf_mf_cli.hpp
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 inline uint64_t sweep_key(uint64_t seed, uint32_t sweep) { return splitmix64(splitmix64(seed) ^ (uint64_t)sweep); }
 

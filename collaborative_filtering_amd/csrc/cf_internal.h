@@ -140,6 +140,10 @@ struct cf_ctx {
     void* d_prep = nullptr;
     size_t prep_bytes = 0;
     hipEvent_t prep_ev[2] = {nullptr, nullptr};
+    // hold-out split (cf_split.hip): events around the steps of the last call (cf_split_timing):
+    // start, keys + sort + by-item lists, core rounds, order sorts, parts + stats
+    hipEvent_t split_ev[5] = {};
+    int split_steps = 0;   // steps the last call recorded (2: cf_kcore, 4: cf_holdout_split, 0: none)
     // bucket overlap (eigen, predict): kAuxStreams non-blocking streams, a join event per
     // stream and one fork event (cf_eigen.hip, cf_predict.hip)
     static constexpr int kAuxStreams = 2;   // measured: 3 streams no faster at C2

@@ -31,6 +31,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "cf_internal.h"
+#include "cf_prep_scratch.h"   // grid_for, Carve, prep_reserve, prep_events
 #include "cf_sort.h"   // SortCfg, sort_pairs, sort_keys, bits_for: the stable merge-sort path
 
 namespace {
@@ -186,36 +187,6 @@ __global__ void fold_keys_kernel(uint64_t n, const uint32_t* user, const uint32_
         key[i] = rank[user[i]];
         idx[i] = (uint32_t)i;
     }
-}
-
-inline dim3 grid_for(uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 65536))); }
-
-// Bump allocator over the context's prep scratch (grown to the request, 256 B aligned).
-struct Carve {
-    char* base;
-    size_t used = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + used);
-        used += (sizeof(T) * std::max<size_t>(count, 1) + 255) & ~size_t(255);
-        return p;
-    }
-};
-
-int prep_reserve(cf_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->prep_bytes) return CF_OK;
-    if (ctx->d_prep) (void)hipFree(ctx->d_prep);
-    ctx->d_prep = nullptr;
-    ctx->prep_bytes = 0;
-    if (hipMalloc(&ctx->d_prep, bytes) != hipSuccess) return cf_set_error(ctx, CF_ENOMEM, "prep scratch");
-    ctx->prep_bytes = bytes;
-    return CF_OK;
-}
-
-int prep_events(cf_ctx* ctx) {
-    for (hipEvent_t& e : ctx->prep_ev)
-        if (!e) CF_HIP_CHECK(ctx, hipEventCreate(&e));
-    return CF_OK;
 }
 
 // cub temporary-storage sizes, queried with exactly the arguments of the real calls (rocprim

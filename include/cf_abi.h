@@ -494,7 +494,57 @@ int cf_fold_order(cf_ctx* ctx, uint64_t n, uint32_t n_users, const uint32_t* use
                   uint32_t* order);
 int cf_fold_order_run(cf_ctx* ctx, uint64_t n, uint32_t n_users, const uint32_t* d_user, const uint32_t* d_rank,
                       uint32_t* d_order, void* stream);
-/* Device time (HIP events) of the last cf_knn_regroup(_run) / cf_fold_order(_run); waits. */
+/* Per-user hold-out split and k-core filter (cf_split.hip; no counterpart in the reference, whose
+ * only splitter is the user-disjoint one above).  Input: n < 2^31 edges in read order with compact
+ * ids user[i] < n_users, item[i] < n_items and, optionally, order_key[i].  Integers throughout.
+ *   1. duplicates: of the edges with one (user, item) the last one read is kept (the rule of
+ *      cf_knn_regroup); the others are dropped.  A kept edge carries its own order_key.
+ *   2. k-core (min_user, min_item; 0 or 1: no limit on that side), in synchronous rounds over the
+ *      kept edges: the degree of every vertex is counted over the edges alive after the previous
+ *      round, every user below min_user and every item below min_item dies, and so does every edge
+ *      with a dead end.  The rounds stop at the first one in which no edge dies; *rounds counts
+ *      those in which one did.  What is left is the maximal core, a function of the edge set alone.
+ *   3. order within a user: its n_u alive edges by (order_key, item) ascending; with order_key ==
+ *      NULL the key is sm(sm(sm(seed) ^ user) ^ item), sm = splitmix64 (as in cf_bpr_fit), a
+ *      function of the ids, so a split does not depend on the read order.
+ *   4. parts, p = the edge's position in that order, t = max(n_u - min_train, 0):
+ *        CF_SPLIT_LEAVE_K  a = K           h_u = min(K, t)                     part = p < h_u
+ *        CF_SPLIT_RATIO    a / b, 0<a<b    h_u = min(floor(n_u a / b), t)      part = p < h_u
+ *        CF_SPLIT_FOLDS    a = F, 2..254   part = p mod F
+ *      part 1 is VALIDATE, part 0 TRAIN; dropped and dead edges get CF_SPLIT_DROPPED.
+ * The core runs before the hold-out, so a TRAIN degree may end below the core's limit.
+ * cf_kcore is steps 1-2: keep[i] = 1 for the edges alive after the core, in read order.
+ * cf_holdout_split is steps 1-4: part[i] in read order and stats[CF_SPLIT_STATS] (may be NULL):
+ *   [0] edges kept after duplicates  [1] edges alive after the core  [2] users, [3] items alive
+ *   [4] edges of part 0 (TRAIN)  [5] edges of part 1 (VALIDATE)
+ *   [6] alive items without a TRAIN edge (0 for folds)  [7] rounds
+ * CF_EINVAL: an id out of range, a null array with n > 0, an unknown mode or parameters outside
+ * the ranges above; CF_ERANGE: n >= 2^31.  n = 0 is valid.  The _run forms take device arrays
+ * (rounds stays a host pointer) and wait for the stream: one word is read back per round. */
+#define CF_SPLIT_LEAVE_K 0
+#define CF_SPLIT_RATIO 1
+#define CF_SPLIT_FOLDS 2
+#define CF_SPLIT_DROPPED 255
+#define CF_SPLIT_STATS 8
+int cf_kcore(cf_ctx* ctx, uint64_t n, uint32_t n_users, uint32_t n_items, const uint32_t* user,
+             const uint32_t* item, uint32_t min_user, uint32_t min_item, uint8_t* keep, uint32_t* rounds);
+int cf_kcore_run(cf_ctx* ctx, uint64_t n, uint32_t n_users, uint32_t n_items, const uint32_t* d_user,
+                 const uint32_t* d_item, uint32_t min_user, uint32_t min_item, uint8_t* d_keep, uint32_t* rounds,
+                 void* stream);
+int cf_holdout_split(cf_ctx* ctx, uint64_t n, uint32_t n_users, uint32_t n_items, const uint32_t* user,
+                     const uint32_t* item, const uint64_t* order_key, uint64_t seed, uint32_t min_user,
+                     uint32_t min_item, int mode, uint32_t a, uint32_t b, uint32_t min_train, uint8_t* part,
+                     uint64_t* stats);
+int cf_holdout_split_run(cf_ctx* ctx, uint64_t n, uint32_t n_users, uint32_t n_items, const uint32_t* d_user,
+                         const uint32_t* d_item, const uint64_t* d_order_key, uint64_t seed, uint32_t min_user,
+                         uint32_t min_item, int mode, uint32_t a, uint32_t b, uint32_t min_train, uint8_t* d_part,
+                         uint64_t* d_stats, void* stream);
+/* Device time of the steps of the last cf_kcore(_run) / cf_holdout_split(_run): ms[0] keys, sort,
+ * duplicates and the by-item lists, ms[1] the core rounds (with their read-backs), ms[2] the two
+ * order sorts, ms[3] parts and stats (ms[2], ms[3] are 0 after cf_kcore); waits. */
+int cf_split_timing(cf_ctx* ctx, float ms[4]);
+/* Device time (HIP events) of the last cf_knn_regroup(_run) / cf_fold_order(_run) / cf_kcore(_run) /
+ * cf_holdout_split(_run); waits. */
 int cf_prep_timing(cf_ctx* ctx, float* ms);
 
 /* ---- graph-signal polynomial filters ------------------------ */
